@@ -9,7 +9,10 @@ Multi-GPU: one process per GPU (torch.distributed.run); chains are independent, 
 own `--chains` chains with no collective on the data path; the posterior draws of the timed steps are
 all-gathered over RCCL at the end of the timed region (pmcmc chain gather).
 
-Also reported: roofline of the dominant kernel (pf_step_kernel, HIP-event timed on the engine's stream),
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps, writes the last step's outputs where
+`--dump-outputs DIR` asks for them, and prints the headline line; nothing else.
+
+Reported only with `--full`: roofline of the dominant kernel (pf_step_kernel, HIP-event timed on the engine's stream),
 a CPU baseline (the oracle C restatement, OpenMP, on a bounded sample) on rank 0 at N=1, and `configs`: short
 timed runs of the other BASELINE workloads -- config 1 at 6,144 chains per GPU, configs 3, 4, 5 at 256 and config 5 at ONE chain per
 GPU (BASELINE's "8 independent chains across 8 GPUs" layout, the lane-group kernel) -- each with its own roofline where
@@ -50,6 +53,14 @@ def parse():
     ap.add_argument("--proposal", choices=["config", "fixed_theta"], default="config",
                     help="MH proposal h * sigma: the config's (epipf.datasets.PROPOSALS) or h = 1e-4, sigma = I")
     ap.add_argument("--seed", type=int, default=2024)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else the bench reports: the device-counters "
+                         "iteration and the rooflines, one chain per GPU and speculative MH, the `configs` workloads, the "
+                         "CPU baselines; and write the detail file.  Without it: set up, warm up, time --steps MH "
+                         "iterations, print the headline line (the options below then have no effect)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed MH iteration returned (rank 0's chains: thetas, log-likelihoods, "
+                         "likelihoods, sampled trajectories) and the gathered draws as DIR/<name>.npy (float64)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--single-chain", action=argparse.BooleanOptionalAction, default=True,
@@ -243,10 +254,10 @@ def proposal(meta, kind):
 
 
 
-def timed_chains(ctx, args, cfg, chains, steps, warmup, kind, pipelines=1, streams_env=4):
+def timed_chains(ctx, args, cfg, chains, steps, warmup, kind, pipelines=1, streams_env=4, counters=True):
     """`chains` independent MH chains per rank of BASELINE config `cfg`: warmup, then `steps` timed MH iterations
-    between barriers (+ the end-of-run RCCL all-gather of the draws), then one untimed iteration with the device
-    counters on.  Returns a dict of what the bench line reports."""
+    between barriers (+ the end-of-run RCCL all-gather of the draws), then (`counters`) one untimed iteration with the
+    device counters on.  Returns a dict of what the bench line reports."""
     from epipf import _lib, datasets
     from epipf.distributed import gather_draws, shard
     from epipf.engine import Engine
@@ -303,14 +314,17 @@ def timed_chains(ctx, args, cfg, chains, steps, warmup, kind, pipelines=1, strea
     dt = time.perf_counter() - t0
     a1, f1 = accept_counts()
     st = stats_sum()
-    # one extra, untimed MH iteration with device counters on: SSA events/s and SIMD lane use
-    for e in engines:
-        e.reset_stats()
-        e.set_profiling(_lib.PROFILE_COUNTERS)
-    run_pipelined(samplers, 1) if P > 1 else samplers[0].step()
+    last = samplers[0].i - 1                       # the last timed MH iteration's row of every sampler's arrays
+    cst = {}
+    if counters:
+        # one extra, untimed MH iteration with device counters on: SSA events/s and SIMD lane use
+        for e in engines:
+            e.reset_stats()
+            e.set_profiling(_lib.PROFILE_COUNTERS)
+        run_pipelined(samplers, 1) if P > 1 else samplers[0].step()
+        cst = stats_sum()
     for e in engines:
         e.set_profiling(_lib.PROFILE_OFF)
-    cst = stats_sum()
     dt_max, filters_all = ctx.max_sum(dt, filters)
     lanes = int(engines[0].stats()["last_lanes"]) or 1
     # the path every engine took on its last run: the roofline's launch arithmetic assumes one path for all of them
@@ -321,7 +335,7 @@ def timed_chains(ctx, args, cfg, chains, steps, warmup, kind, pipelines=1, strea
     return dict(Y=Y, meta=meta, N=N, T=T, chains=chains, P=P, streams=streams, samplers=samplers, engines=engines,
                 fused=fused, paths=paths,
                 dt=dt_max, filters=filters, filters_all=filters_all, value=filters_all * N * T / dt_max, st=st, cst=cst,
-                lanes=lanes, h=h, sigma=sigma, proposal=pdesc, gathered=gathered,
+                lanes=lanes, h=h, sigma=sigma, proposal=pdesc, gathered=gathered, last=last,
                 acceptance_rate=(a1 - a0) / max(1, f1 - f0), steps=steps, warmup=warmup)
 
 
@@ -662,6 +676,36 @@ def write_detail(full, path):
     return os.path.relpath(path, REPO) if os.path.abspath(path).startswith(REPO) else path
 
 
+DUMP_LIMIT = 64 << 20      # bytes of all --dump-outputs arrays together
+
+
+def timed_outputs(run):
+    """What a caller of the timed path holds after its last timed MH iteration: per chain of this rank (samplers in
+    chain order) the iteration's theta, log-likelihood, likelihood and sampled trajectory ([chains, T, C]), and the
+    draws of every rank's chains up to that iteration as gathered at the end of the timed region."""
+    i, samplers = run["last"], run["samplers"]
+    return {"thetas": np.concatenate([s.thetas[:, i] for s in samplers]),
+            "log_likelihoods": np.concatenate([s.loglik[:, i] for s in samplers]),
+            "likelihoods": np.concatenate([s.likelihoods[:, i] for s in samplers]),
+            "trajectories": np.concatenate([s._tr[:, i] for s in samplers]),
+            "gathered_draws": np.asarray(run["gathered"])}
+
+
+def dump_outputs(outputs, path, limit=DUMP_LIMIT):
+    """Write {name: array} as path/<name>.npy in float64, at most `limit` bytes in all: an array over its equal share
+    keeps a fixed, seeded sample of its rows (first axis), whose indices go to <name>_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    share = limit // (2 * max(1, len(outputs)))                   # half of each share is room for the row indices
+    for name, a in outputs.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.nbytes > share and a.ndim >= 1 and a.shape[0] > 1:
+            keep = max(1, share // max(1, a[0].nbytes))
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], size=min(keep, a.shape[0]), replace=False))
+            a = a[rows]
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     args = parse()
     msg = resolve_gpus(args, os.environ)
@@ -706,16 +750,68 @@ def main():
     N0, T0 = (args.particles or meta0["N"]), Y.shape[0]
     pipelines = args.pipelines or 1                  # > 1: chain groups' host work overlapping (run_pipelined)
     streams_env = max(1, min(int(os.environ.get("EPIPF_STREAMS", 4)), 8))
-    run = timed_chains(ctx, args, args.config, C, args.steps, args.warmup, args.proposal, pipelines, streams_env)
+    run = timed_chains(ctx, args, args.config, C, args.steps, args.warmup, args.proposal, pipelines, streams_env,
+                       counters=args.full)
     run["cfg"] = args.config
     meta, N, T, P, st, cst = run["meta"], run["N"], run["T"], run["P"], run["st"], run["cst"]
     value, dt = run["value"], run["dt"]
     lanes = run["lanes"]
+    gathered = run["gathered"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(timed_outputs(run), args.dump_outputs)
+
+    def headline():
+        """The timed region's own figures: all of a plain run's line, the head of a --full run's."""
+        # distinct GPUs, not ranks: (host, device) pairs over all ranks (gloo rehearsals put several ranks on one)
+        n_gpus = len({tuple(d) for d in devices})
+        return {
+            "metric": f"particle-steps/sec (N_particles x T_obs x MH-iters) on {MODEL_NAMES[meta['model']]} PMCMC",
+            "value": value,
+            "unit": "particle-steps/s",
+            "n_gpus": n_gpus,
+            "ranks": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": dt * 1e3 / args.steps,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": f"synthetic ({meta['describe']}); Philox-keyed filter draws",
+            "config": {"workload": f"BASELINE config {args.config}: {meta['model'].upper()} PMCMC, N={N} particles, "
+                                   f"pop={meta['n_population']}, {T} obs, {C} independent chains per GPU",
+                       "particles": N, "T_obs": T, "chains_per_gpu": C, "population": meta["n_population"],
+                       "pipelines": P,
+                       "parallelism": f"chains sharded over {n_gpus} GPU(s) ({world} rank(s)), RCCL all-gather of "
+                                      f"draws at end"},
+            "proposal": {"h": run["h"], "sigma": run["sigma"], "kind": args.proposal, "source": run["proposal"],
+                         "acceptance_rate": run["acceptance_rate"]},
+            "kernel": kernel_name(run),
+            "lanes_per_particle": lanes,
+            "resample_fallbacks": st["resample_fallbacks"],
+            "library_build_id": _lib.build_id(),
+            # every rank's posterior draws after the RCCL all-gather
+            "gathered_draws_shape": list(gathered.shape),
+            "rank_devices": [f"{h}:{d}" for h, d in devices],
+        }
+
+    if not args.full:
+        # a plain run ends here: the headline alone (the detail file only where --detail names one)
+        if rank == 0:
+            line = headline()
+            if args.detail:
+                line["detail"] = write_detail(line, args.detail)
+            print(json.dumps(line), flush=True)
+        run["samplers"] = run["engines"] = None
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     roof = roofline(run, value)
     # SSA events per second of job time: events per particle-step (counters iteration) x the measured rate
     events_per_s = value * cst["events"] / cst["particle_steps"] if cst["particle_steps"] else None
     lane_use = cst["lane_iterations"] / cst["wave_lane_slots"] if cst["wave_lane_slots"] else None
-    gathered = run["gathered"]
     # Gelman-Rubin R-hat (helpers.py:15-43) of the gathered chains' timed draws: a bench run is tens of iterations
     # from a fixed start, far too short for a convergence diagnostic, so it is reported, not judged
     rhat = None
@@ -752,51 +848,24 @@ def main():
         base = cpu_baseline(Y, meta, N, args.cpu_baseline_seconds, args.config)
 
     if rank == 0:
-        # distinct GPUs, not ranks: (host, device) pairs over all ranks (gloo rehearsals put several ranks on one)
-        n_gpus = len({tuple(d) for d in devices})
         line = {
-            "metric": f"particle-steps/sec (N_particles x T_obs x MH-iters) on {MODEL_NAMES[meta['model']]} PMCMC",
-            "value": value,
-            "unit": "particle-steps/s",
-            "n_gpus": n_gpus,
-            "ranks": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt * 1e3 / args.steps,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": f"synthetic ({meta['describe']}); Philox-keyed filter draws",
-            "config": {"workload": f"BASELINE config {args.config}: {meta['model'].upper()} PMCMC, N={N} particles, "
-                                   f"pop={meta['n_population']}, {T} obs, {C} independent chains per GPU",
-                       "particles": N, "T_obs": T, "chains_per_gpu": C, "population": meta["n_population"],
-                       "pipelines": P,
-                       "parallelism": f"chains sharded over {n_gpus} GPU(s) ({world} rank(s)), RCCL all-gather of "
-                                      f"draws at end"},
-            "proposal": {"h": run["h"], "sigma": run["sigma"], "kind": args.proposal, "source": run["proposal"],
-                         "acceptance_rate": run["acceptance_rate"]},
+            **headline(),
             "roofline": roof,
             "events_per_s": events_per_s,
             "ssa_lane_utilisation": lane_use if lanes == 1 else None,
-            "lanes_per_particle": lanes,
-            "resample_fallbacks": st["resample_fallbacks"],
             # draws of the untimed counters iteration whose uniform lies within scipy's error envelope of a CDF
             # boundary: the only draws where the reference's own weights could pick another ancestor;
             # of that iteration's resampling draws (the test runs with the device counters only)
             "resample_ref_ambiguous": cst["resample_ref_ambiguous"],
             "resample_draws": cst["particle_steps"] * (T - 1) // T,
-            "library_build_id": _lib.build_id(),
             "pmc_profile": {"build_id": roof["pmc_profile"]["build_id"], "path": roof["pmc_profile"]["path"],
                             "current": roof["pmc_profile"]["path"] is not None},
             "events_per_particle_step": cst["events"] / cst["particle_steps"] if cst["particle_steps"] else None,
             # particle-steps the certified f32 SSA path handed to the exact loop, and waves that waited on one
             "ssa_exact_particle_frac": cst["ssa_exact_lanes"] / cst["particle_steps"] if cst["particle_steps"] else None,
             "ssa_exact_wave_frac": cst["ssa_exact_waves"] * 64 / cst["particle_steps"] if cst["particle_steps"] else None,
-            # every rank's posterior draws after the RCCL all-gather, and their Gelman-Rubin R-hat per parameter
-            "gathered_draws_shape": list(gathered.shape),
+            # Gelman-Rubin R-hat per parameter of every rank's draws after the RCCL all-gather
             "gathered_rhat": rhat,
-            "rank_devices": [f"{h}:{d}" for h, d in devices],
             "configs": configs,
             "cpu_baseline": base,
         }

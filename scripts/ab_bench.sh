@@ -5,6 +5,8 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/ab
 ROOT=$(pwd)
+# --full: the roofline figures read below
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 for i in ${ROUNDS:-1 2}; do
   for side in A B; do
     dir=$ROOT; [ $side = A ] && dir=$ROOT/${AB_DIR:-ab_old}

@@ -4,6 +4,8 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/ab
+# --full: the counters iteration behind the lane-use and events figures read below
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 i=0
 for e in ${ENVS:--}; do
   i=$((i+1))

@@ -9,7 +9,7 @@ TAG=${TAG:-r1}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 rm -f $OUT/count_*.txt
-BENCH="bench.py --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline --no-single-chain --configs none ${BENCH_ARGS:-}"
+BENCH="bench.py --full --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline --no-single-chain --configs none ${BENCH_ARGS:-}"
 K=${PMC_KERNEL:-pf_step_kernel}
 step() {  # step <name> <timeout> <cmd...>
     local name=$1 t=$2; shift 2

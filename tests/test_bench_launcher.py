@@ -84,7 +84,7 @@ def test_bench_north_star_layout_four_gloo_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["EPIPF_DIST_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "4", "--config", "5", "--chains", "1",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--configs", "none"], env=env,
+                        "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--configs", "none"], env=env,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     assert "launching 4 ranks" in r.stderr
@@ -95,3 +95,38 @@ def test_bench_north_star_layout_four_gloo_ranks():
     assert d["gathered_draws_shape"][0] == 4
     assert d["lanes_per_particle"] > 1 and d["roofline"]["kernel"].startswith("pf_step_group_kernel")
     assert d["config"]["chains_per_gpu"] == 1 and d["proposal"]["h"] == 1.0
+
+
+@pytest.mark.gpu
+def test_plain_bench_is_the_headline_alone_and_its_outputs_repeat(tmp_path, monkeypatch, capsys):
+    """A plain run (no --full) prints the headline figures without the rooflines, `configs` or CPU baselines, and
+    --dump-outputs writes the last timed iteration's arrays: two runs with the same arguments give the same arrays."""
+    import json
+
+    import numpy as np
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "EPIPF_BENCH_DIST"):
+        monkeypatch.delenv(k, raising=False)
+    lines = []
+    for d in ("a", "b"):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--config", "1", "--chains", "24", "--steps", "3",
+                                          "--warmup", "1", "--dump-outputs", str(tmp_path / d)])
+        bench.main()
+        out = [x for x in capsys.readouterr().out.splitlines() if x.startswith("{")]
+        assert len(out) == 1
+        lines.append(json.loads(out[0]))
+    line = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["value"] > 0 and line["ms_per_step"] > 0
+    for k in ("roofline", "configs", "cpu_baseline", "single_chain_value", "events_per_s"):
+        assert k not in line, k
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert names == ["gathered_draws.npy", "likelihoods.npy", "log_likelihoods.npy", "thetas.npy", "trajectories.npy"]
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float64 and np.array_equal(a, b), n
+    th, tr, g = (np.load(tmp_path / "a" / n) for n in ("thetas.npy", "trajectories.npy", "gathered_draws.npy"))
+    assert th.shape == (24, 2) and tr.shape[0] == 24 and np.isfinite(tr).all() and tr.any()
+    # the gathered rows are (thetas of iterations 0..i flattened, log-likelihoods): initial draw + warm-up + 3 steps
+    assert g.shape == (24, 5 * 2 + 5) and np.array_equal(g[:, 8:10], th)

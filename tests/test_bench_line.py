@@ -142,3 +142,51 @@ def test_loop_ceiling_parse_reads_the_runs(tmp_path):
     assert u["lane_events_per_s"] == 6.0e11 and abs(u["valu_instr_per_s"] - (6.0e8 + 3) / 1e-3) < 1.0
     assert abs(u["clock_ghz"] - 2.4) < 1e-9 and abs(u["valu_busy"] - 4 * 6.0e8 / (1024 * 2.4e6)) < 1e-9
     assert d["configs"]["2"]["distinct"]["valu_instr_per_s"] == (6.0e8 + 7) / 1e-3
+
+
+def test_dump_outputs_writes_float64_arrays_and_samples_large_ones(tmp_path):
+    """--dump-outputs: every array as <name>.npy in float64; one over its share of the byte limit keeps a fixed,
+    seeded sample of its rows, the same rows on every call, with their indices beside it."""
+    import numpy as np
+    small = np.arange(12, dtype=np.float32).reshape(4, 3)
+    big = np.arange(1000 * 16, dtype=np.float64).reshape(1000, 16)
+    for d in ("a", "b"):
+        bench.dump_outputs({"small": small, "big": big}, str(tmp_path / d), limit=64 * 1024)
+    a = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    b = {f: np.load(tmp_path / "b" / f) for f in sorted(os.listdir(tmp_path / "b"))}
+    assert sorted(a) == ["big.npy", "big_rows.npy", "small.npy"] == sorted(b)
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 * 1024
+    assert np.array_equal(a["small.npy"], small)
+    rows = a["big_rows.npy"].astype(int)
+    assert 1 < len(rows) < 1000 and len(set(rows)) == len(rows) and np.array_equal(a["big.npy"], big[rows])
+    assert all(np.array_equal(a[f], b[f]) for f in a)
+
+
+def test_timed_outputs_are_the_last_timed_iterations_rows():
+    """The dumped arrays are row `last` of every sampler's per-iteration arrays, samplers in chain order, and the
+    gathered draws -- not the later row an untimed counters iteration (--full) appends."""
+    import types
+    import numpy as np
+    rng = np.random.RandomState(3)
+
+    def sampler(nc):
+        return types.SimpleNamespace(thetas=rng.rand(nc, 5, 2), loglik=rng.rand(nc, 5), likelihoods=rng.rand(nc, 5),
+                                     _tr=rng.rand(nc, 5, 7, 3))
+    s = [sampler(2), sampler(3)]
+    g = rng.rand(5, 12)
+    out = bench.timed_outputs({"last": 3, "samplers": s, "gathered": g})
+    assert set(out) == {"thetas", "log_likelihoods", "likelihoods", "trajectories", "gathered_draws"}
+    assert out["thetas"].shape == (5, 2) and out["trajectories"].shape == (5, 7, 3)
+    assert np.array_equal(out["thetas"][2:], s[1].thetas[:, 3]) and np.array_equal(out["log_likelihoods"][:2], s[0].loglik[:, 3])
+    assert np.array_equal(out["trajectories"][:2], s[0]._tr[:, 3]) and out["gathered_draws"] is not None
+    assert np.array_equal(out["gathered_draws"], g)
+
+
+def test_full_is_an_option_and_off_by_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
