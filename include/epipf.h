@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define EPIPF_ABI_VERSION 8
+#define EPIPF_ABI_VERSION 9
 
 /* return codes */
 #define EPIPF_OK 0
@@ -100,7 +100,8 @@ typedef struct {
                                     with the lanes automatic); 0: one launch per filter step */
 } epipf_stats;
 
-/* groups: G for the subgroup models (1 <= G <= 4), ignored (1) for SIR/SEIR.
+/* groups: G for the subgroup models (1 <= G <= epipf_max_groups() = 8), ignored (1) for SIR/SEIR.  G = 5..8 run one
+ * lane per particle at every size (the lane-group and one-workgroup kernels exist for G <= 4).
  * t_max: largest T (observation rows) a run may use; max_chains: largest batch of independent filters. */
 int epipf_create(epipf_ctx** out, int device, int model, int groups, int n_particles, int t_max,
                  int max_chains);
@@ -210,7 +211,8 @@ int epipf_set_streams(epipf_ctx* ctx, int n_streams);
    particle (throughput: batches that fill the chip), 2/4/8/16 = a group of lanes draws consecutive events' Philox
    blocks in parallel and runs only the sequential decisions event by event (latency: a single chain or a few chains,
    DESIGN.md §12).  events_per_lane: events each lane of a group draws per chunk (0 = automatic).  Engine tuning only,
-   no reference counterpart; results are identical for every value. */
+   no reference counterpart; results are identical for every value.  lanes > 1 on a context with G > 4 is EPIPF_EINVAL
+   (lane groups exist for G <= 4), as is EPIPF_LANES > 1 at its creation. */
 int epipf_set_lanes(epipf_ctx* ctx, int lanes, int events_per_lane);
 int epipf_get_stats(epipf_ctx* ctx, epipf_stats* out);
 int epipf_reset_stats(epipf_ctx* ctx);
@@ -235,6 +237,8 @@ int epipf_mh_peek(int n, const int32_t* chains, void* const* mt_states, int n_pa
 
 const char* epipf_last_error(void);
 int epipf_abi_version(void);
+/* Largest G the subgroup models accept (8). */
+int epipf_max_groups(void);
 /* Hash of the library's sources and build flags (16 hex digits; "...-debug" for libepipf_debug.so).  Profiles taken
  * on one build are trusted by bench.py only for the same id. */
 const char* epipf_build_id(void);

@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
@@ -145,6 +146,7 @@ struct epipf_ctx {
 // blocks (pick_block) the subgroup models keep W = 16 up to four chains (+27% over W = 8 at three and four) and SIR /
 // SEIR take W = 8 up to six (+11% / +7% over W = 4 at six; profiles/r4aa_lanes_sweep.txt).
 static int pick_lanes(const epipf_ctx* c, int n_chains) {
+    if (c->G > kMaxLaneG) return 1;                      // no lane-group kernels for G = 5..8 (epipf_kernels_wide.hip)
     if (c->lanes > 0) return c->lanes;
     const long blocks = (long)n_chains * c->B, lb = c->lane_blocks;
     if (c->model == EPIPF_SIR || c->model == EPIPF_SEIR)
@@ -186,7 +188,7 @@ static int pick_group_lone(const epipf_ctx* c, const StepArgs& a, int n_chains) 
 // kFusedMaxN with the lanes automatic (an explicit epipf_set_lanes / EPIPF_LANES keeps the step kernels it names) and
 // the chain's LDS within the default launch limit.  W: EPIPF_FUSED_LANES where its N W lanes fit one workgroup, else 1.
 static int pick_fused(const epipf_ctx* c) {
-    if (!c->fused || c->lanes > 0 || c->N > kFusedMaxN) return 0;
+    if (!c->fused || c->lanes > 0 || c->N > kFusedMaxN || c->G > kMaxLaneG) return 0;   // (no such kernel for G = 5..8)
     const int W = (c->fused_lanes > 0 && c->N * c->fused_lanes <= kFusedMaxThreads) ? c->fused_lanes : 1;
     if (fused_lds_bytes_of(c->N, c->C, fused_threads_of(c->N, W), 0, 0) > kFusedLdsLimit) return 0;
     return W;
@@ -304,6 +306,26 @@ static double ref_pmf_envelope(int obs_model, int n_max) {
     return 4e-12 + 1e-16 * (double)std::max(n_max, 0);
 }
 
+// parameter i of a chain: in ChainParam for the models up to kMaxLaneG groups, in the chain's WideParam block (w, or
+// null) for the wider ones
+static void set_theta(ChainParam& q, WideParam* w, int i, double v) {
+    if (w) { w->theta[i] = v; w->thetaf[i] = (float)v; }
+    else { q.theta[i] = v; q.thetaf[i] = (float)v; }
+}
+
+// ChainParam slots of an array of n chains' parameters: n, plus the room of n WideParam blocks behind them for a
+// context with G > kMaxLaneG (wide_param, epipf_device.hpp)
+static size_t cp_slots(int G, size_t n) {
+    return n + (G > kMaxLaneG ? (n * sizeof(WideParam) + sizeof(ChainParam) - 1) / sizeof(ChainParam) : 0);
+}
+static_assert(sizeof(ChainParam) % alignof(WideParam) == 0, "WideParam blocks start behind a ChainParam array");
+// one chain's parameters with its block, as epipf_simulate / epipf_simulate_path upload them
+struct OneChain {
+    ChainParam q;
+    WideParam w;
+};
+static_assert(offsetof(OneChain, w) == sizeof(ChainParam), "wide_param(cp, 1, 0)");
+
 static int theta_dim(int model, int G) { return model == EPIPF_SIR ? 2 : model == EPIPF_SEIR ? 3 : G * G + 1; }
 
 static void free_ctx(epipf_ctx* c) {
@@ -348,6 +370,7 @@ extern "C" {
 
 const char* epipf_last_error(void) { return g_err.c_str(); }
 int epipf_abi_version(void) { return EPIPF_ABI_VERSION; }
+int epipf_max_groups(void) { return kMaxG; }
 static_assert(kStatusOk == EPIPF_STATUS_OK && kStatusDegenerate == EPIPF_STATUS_DEGENERATE &&
               kStatusSkipped == EPIPF_STATUS_SKIPPED, "device status codes");
 const char* epipf_build_id(void) {
@@ -392,6 +415,10 @@ int epipf_create(epipf_ctx** out, int device, int model, int groups, int n_parti
     if (const char* e = getenv("EPIPF_LANES")) {
         const int w = atoi(e);
         if (w == 0 || w == 1 || w == 2 || w == 4 || w == 8 || w == 16) c->lanes = w;
+        if (c->lanes > 1 && G > kMaxLaneG) {
+            free_ctx(c);
+            return fail(EPIPF_EINVAL, "EPIPF_LANES=%d with G=%d: lane groups exist for G <= %d", w, G, kMaxLaneG);
+        }
     }
     if (const char* e = getenv("EPIPF_LANE_BLOCKS")) c->lane_blocks = std::max(0, atoi(e));
     if (const char* e = getenv("EPIPF_LANE_EVENTS")) c->lane_events = std::max(0, atoi(e));
@@ -433,13 +460,13 @@ int epipf_create(epipf_ctx** out, int device, int model, int groups, int n_parti
     rc |= dalloc(&c->wraw, 2 * (size_t)max_chains * c->wstride);
     rc |= dalloc(&c->wloc, 2 * (size_t)max_chains * c->wstride);
     rc |= dalloc(&c->bsum, 2 * (size_t)max_chains * c->bstride);
-    rc |= dalloc(&c->cp, (size_t)max_chains);
+    rc |= dalloc(&c->cp, cp_slots(G, (size_t)max_chains));
     rc |= dalloc(&c->logtab, (size_t)kLogTabEntries);
     if (rc) { free_ctx(c); return EPIPF_ENOMEM; }
     c->status = static_cast<int32_t*>(c->res);
     c->counters = reinterpret_cast<unsigned long long*>(static_cast<char*>(c->res) + c->res_counters);
     c->log_zeta = reinterpret_cast<double*>(static_cast<char*>(c->res) + c->res_lz);
-    if (hipHostMalloc((void**)&c->h_cp, sizeof(ChainParam) * max_chains) != hipSuccess ||
+    if (hipHostMalloc((void**)&c->h_cp, sizeof(ChainParam) * cp_slots(G, (size_t)max_chains)) != hipSuccess ||
         hipHostMalloc(&c->h_res, res_bytes) != hipSuccess ||
         hipHostMalloc((void**)&c->h_traj, sizeof(int32_t) * (size_t)max_chains * t_max * c->C) != hipSuccess) {
         free_ctx(c);
@@ -534,12 +561,13 @@ static int run_impl(epipf_ctx* c, int n_chains, const double* theta, int d, int 
         const bool on = !active || active[ch];
         ChainParam& q = c->h_cp[ch];
         memset(&q, 0, sizeof q);
+        WideParam* w = c->G > kMaxLaneG ? const_cast<WideParam*>(wide_param(c->h_cp, c->max_chains, ch)) : nullptr;
+        if (w) memset(w, 0, sizeof *w);
         for (int i = 0; i < d; ++i) {
             const double v = theta[(size_t)ch * d + i];
             if (on && !(v >= 0.0 && v < INFINITY))
                 return fail(EPIPF_EINVAL, "theta[%d][%d]=%g: parameters must be finite and >= 0 (pmcmc.py:333)", ch, i, v);
-            q.theta[i] = v;
-            q.thetaf[i] = (float)v;
+            set_theta(q, w, i, v);
         }
         q.probs = probs[ch];
         if (!(probs[ch] == c->split_p) && !(std::isnan(probs[ch]) && std::isnan(c->split_p))) {   // binary128: ~2 us
@@ -558,6 +586,10 @@ static int run_impl(epipf_ctx* c, int n_chains, const double* theta, int d, int 
         q.flags = (c->fast_ssa ? kChainFastSsa : 0u) | (c->seq_decide ? kChainSeqDecide : 0u);
         q.clock_slack = c->clock_slack;
         q.band_slack = c->band_slack;
+        for (int g = kMaxLaneG; w && g < kMaxG; ++g) {
+            const int h = g - kMaxLaneG;
+            w->npop_hi[h] = c->npop[g]; w->mu_hi[h] = c->mu[g]; w->emu_hi[h] = c->emu[g]; w->kmax_hi[h] = c->kmax[g];
+        }
         q.skip = on ? 0 : 1;                            // the first kernel writes the chain's status from it
         q.chosen = -1;
         if (chosen && on) {
@@ -568,6 +600,9 @@ static int run_impl(epipf_ctx* c, int n_chains, const double* theta, int d, int 
     }
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMemcpyAsync(c->cp, c->h_cp, sizeof(ChainParam) * n_chains, hipMemcpyHostToDevice, c->stream));
+    if (c->G > kMaxLaneG)   // the chains' WideParam blocks, behind the ChainParam array on both sides
+        HIP_TRY(hipMemcpyAsync(const_cast<WideParam*>(wide_param(c->cp, c->max_chains, 0)), wide_param(c->h_cp, c->max_chains, 0),
+                               sizeof(WideParam) * n_chains, hipMemcpyHostToDevice, c->stream));
 
     StepArgs a{};
     a.N = c->N; a.T = c->T; a.max_chains = c->max_chains;
@@ -609,7 +644,7 @@ static int run_impl(epipf_ctx* c, int n_chains, const double* theta, int d, int 
         a.fused_y = base + yb <= kFusedLdsLimit;
         a.fused_lf = a.lf_max >= 0 && base + (a.fused_y ? yb : 0) + lb <= kFusedLdsLimit;
     }
-    for (int g = 0; g < kMaxG; ++g) { a.npop[g] = c->npop[g]; a.mu[g] = c->mu[g]; a.emu[g] = c->emu[g]; a.kmax[g] = c->kmax[g]; }
+    for (int g = 0; g < kMaxLaneG; ++g) { a.npop[g] = c->npop[g]; a.mu[g] = c->mu[g]; a.emu[g] = c->emu[g]; a.kmax[g] = c->kmax[g]; }
 
     EPIPF_RANGE_PUSH("epipf_run");
     struct RangeEnd { ~RangeEnd() { EPIPF_RANGE_POP(); } } range_end;
@@ -791,21 +826,22 @@ int epipf_simulate(epipf_ctx* c, int n, const int32_t* states_in, const double* 
     if (n == 0) { if (events_out) *events_out = 0; return EPIPF_OK; }
     HIP_TRY(hipSetDevice(c->device));
     const size_t sb = align256((size_t)n * c->C * sizeof(int32_t));
-    const size_t need = align256(sizeof(ChainParam)) + 2 * sb + 256;
+    const size_t need = align256(sizeof(OneChain)) + 2 * sb + 256;
     if (ensure_scratch(c, need)) return EPIPF_ENOMEM;
     char* base = (char*)c->scratch;
     ChainParam* dcp = (ChainParam*)base;
-    int32_t* din = (int32_t*)(base + align256(sizeof(ChainParam)));
+    int32_t* din = (int32_t*)(base + align256(sizeof(OneChain)));
     int32_t* dout = (int32_t*)((char*)din + sb);
     unsigned long long* dev_events = (unsigned long long*)((char*)dout + sb);
-    ChainParam q;
-    memset(&q, 0, sizeof q);
-    for (int i = 0; i < d; ++i) { q.theta[i] = theta[i]; q.thetaf[i] = (float)theta[i]; }
+    OneChain one;
+    memset(&one, 0, sizeof one);
+    ChainParam& q = one.q;
+    for (int i = 0; i < d; ++i) set_theta(q, c->G > kMaxLaneG ? &one.w : nullptr, i, theta[i]);
     q.k0 = (uint32_t)key; q.k1 = (uint32_t)(key >> 32); q.f = filter_index;
     q.flags = (c->fast_ssa ? kChainFastSsa : 0u) | (c->seq_decide ? kChainSeqDecide : 0u);
     q.clock_slack = c->clock_slack;
     q.band_slack = c->band_slack;
-    HIP_TRY(hipMemcpyAsync(dcp, &q, sizeof q, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dcp, &one, sizeof one, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(din, states_in, sizeof(int32_t) * (size_t)n * c->C, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(dev_events, 0, sizeof(unsigned long long), c->stream));
     SimArgs a{};
@@ -839,22 +875,23 @@ int epipf_simulate_path(epipf_ctx* c, int n, const int32_t* states_in, const dou
     const size_t sb = align256((size_t)n * C * sizeof(int32_t));
     const size_t tb = align256(cap * n * sizeof(double)), xb = align256(cap * n * C * sizeof(int32_t));
     const size_t nb = align256((size_t)n * sizeof(int32_t));
-    const size_t need = align256(sizeof(ChainParam)) + 2 * sb + tb + xb + nb;
+    const size_t need = align256(sizeof(OneChain)) + 2 * sb + tb + xb + nb;
     if (ensure_scratch(c, need)) return EPIPF_ENOMEM;
     char* base = (char*)c->scratch;
     ChainParam* dcp = (ChainParam*)base;
-    int32_t* din = (int32_t*)(base + align256(sizeof(ChainParam)));
+    int32_t* din = (int32_t*)(base + align256(sizeof(OneChain)));
     int32_t* dfin = (int32_t*)((char*)din + sb);
     double* dt = (double*)((char*)dfin + sb);
     int32_t* dx = (int32_t*)((char*)dt + tb);
     int32_t* dnev = (int32_t*)((char*)dx + xb);
-    ChainParam q;
-    memset(&q, 0, sizeof q);
-    for (int i = 0; i < d; ++i) { q.theta[i] = theta[i]; q.thetaf[i] = (float)theta[i]; }
+    OneChain one;
+    memset(&one, 0, sizeof one);
+    ChainParam& q = one.q;
+    for (int i = 0; i < d; ++i) set_theta(q, c->G > kMaxLaneG ? &one.w : nullptr, i, theta[i]);
     q.k0 = (uint32_t)key; q.k1 = (uint32_t)(key >> 32); q.f = filter_index;
     q.clock_slack = 1.f;
     q.band_slack = 1.f;
-    HIP_TRY(hipMemcpyAsync(dcp, &q, sizeof q, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dcp, &one, sizeof one, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(din, states_in, sizeof(int32_t) * (size_t)n * C, hipMemcpyHostToDevice, c->stream));
     SimPathArgs a{};
     a.logtab = c->logtab; a.n = n; a.cap = max_events; a.step = step; a.tmax = max_time; a.cp = dcp; a.in = din;
@@ -1229,6 +1266,8 @@ int epipf_set_lanes(epipf_ctx* c, int lanes, int events_per_lane) {
     if (events_per_lane < 0) return fail(EPIPF_EINVAL, "events_per_lane %d < 0", events_per_lane);
     if (lanes > 1 && events_per_lane > 0 && !group_shape_supported(lanes, events_per_lane))
         return fail(EPIPF_EINVAL, "no lane-group kernel for %d lanes x %d events per lane", lanes, events_per_lane);
+    if (lanes > 1 && c->G > kMaxLaneG)
+        return fail(EPIPF_EINVAL, "%d lanes per particle with G=%d: lane groups exist for G <= %d", lanes, c->G, kMaxLaneG);
     c->lanes = lanes;
     c->lane_events = events_per_lane;
     return EPIPF_OK;

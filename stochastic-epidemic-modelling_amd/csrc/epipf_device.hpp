@@ -8,11 +8,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace epipf {
 
-constexpr int kMaxG = 4;                    // largest subgroup count instantiated
+constexpr int kMaxG = 8;                    // largest subgroup count instantiated
+constexpr int kMaxLaneG = 4;                // largest with lane-group and one-workgroup kernels (and channel bit masks)
 constexpr int kMaxC = 3 * kMaxG;            // compartments per particle
 constexpr int kMaxTheta = kMaxG * kMaxG + 1;
+constexpr int kLaneTheta = kMaxLaneG * kMaxLaneG + 1;   // parameters of the models up to kMaxLaneG groups
 constexpr uint32_t kDomainSSA = 0u << 24;
 constexpr uint32_t kDomainResample = 1u << 24;
 constexpr uint32_t kDomainInit = 2u << 24;
@@ -85,7 +89,7 @@ __device__ __forceinline__ int checked_index(int i, int n) {
 
 // ------------------------------------------------------------------------------- per-chain parameters
 struct ChainParam {
-    double theta[kMaxTheta];   // SIR: beta,gamma  SEIR: beta,alpha,gamma  groups: beta[G][G], gamma
+    double theta[kLaneTheta];  // SIR: beta,gamma  SEIR: beta,alpha,gamma  groups: beta[G][G], gamma (G > 4: WideParam)
     double probs;              // binomial p, or normal noise ratio
     double logp, log1mp;       // log(p), log1p(-p): hi parts of their binary128 values (logfact.cpp)
     double logp_lo, log1mp_lo; //   and the lo parts (binom_logpmf)
@@ -95,11 +99,32 @@ struct ChainParam {
     uint32_t flags;            // kChainFastSsa: the certified f32 event loop may run (EPIPF_SSA_FAST=0 clears it)
     int32_t skip;              // 1: this chain runs no filter in this batch (epipf_run's active[] = 0)
     int32_t chosen;            // epipf_run_sampled: the path sampler's final particle (pmcmc.py:241), -1: none
-    float thetaf[kMaxTheta];   // theta rounded to f32 on the host (scalar loads: the fast path's rates stay in SGPRs)
+    float thetaf[kLaneTheta];  // theta rounded to f32 on the host (scalar loads: the fast path's rates stay in SGPRs)
     float clock_slack;         // >= 1: widens the f32 loop's clock band (more replays, same results); tests only
     float band_slack;          // >= 1: widens the channel decision's band (more exact decisions and redone chunks,
                                // same results); tests only
 };
+// A uniform read-only pointer as the constant address space: its loads are scalar loads (SGPRs) wherever they stand,
+// also after the kernel's own stores.  Only for memory no kernel writes (the per-chain parameters).
+#define EPIPF_CONSTANT __attribute__((address_space(4)))
+
+// Per-chain parameters of the subgroup models at G > kMaxLaneG, in a block of their own: ChainParam (and StepArgs) stay
+// byte for byte what the kernels of the narrower models were compiled against -- appending these fields to ChainParam
+// changed those kernels' spills and scratch (profiles/wide_groups_resources.txt).  The blocks follow the ChainParam
+// array in the same device allocation (wide_param); the wide kernels hand their chain's block to the states (bind), which
+// read the rates through it at the point of use.
+struct WideParam {
+    double theta[kMaxTheta];   // beta[G][G] row-major, then gamma
+    float thetaf[kMaxTheta];   //   rounded to f32 on the host
+    // groups kMaxLaneG..kMaxG-1 (groups 0..3 are kernel arguments, StepArgs): population, Poisson mean, exp(-mean) and
+    // the inversion's cap
+    double npop_hi[kMaxG - kMaxLaneG], mu_hi[kMaxG - kMaxLaneG], emu_hi[kMaxG - kMaxLaneG];
+    int32_t kmax_hi[kMaxG - kMaxLaneG];
+};
+// chain `chain`'s block behind an array of n_cp ChainParam
+__host__ __device__ inline const WideParam* wide_param(const ChainParam* cp, int n_cp, int chain) {
+    return reinterpret_cast<const WideParam*>(cp + n_cp) + chain;
+}
 // chain status codes (include/epipf.h's EPIPF_STATUS_*; epipf_api.cpp checks they agree)
 constexpr int32_t kStatusOk = 0, kStatusDegenerate = 1, kStatusSkipped = 2;
 constexpr uint32_t kChainFastSsa = 1u;   // (all models)
@@ -423,8 +448,143 @@ struct SubgroupsState {                                                // gilles
         return rates(cp, cum) * neg_log_one_minus_u01(r.x, r.y, tab);
     }
 };
-template <int G> struct SsaState<kSubgroups, G> : SubgroupsState<G> {};
-template <int G> struct SsaState<kSubgroups2, G> : SubgroupsState<G> {};
+// ---- G > kMaxLaneG (up to 72 channels): the same arithmetic without a per-lane array of NCH doubles.
+// Every pass over the channels recomputes a_i with the reference's expression in the reference's order, so each
+// running sum is the array form's, bit for bit (no contraction, recomputation is deterministic).  The passes are
+// loops over the infecting group g (kept rolled: 9 terms of code, not 72): g is wave-uniform, so I[g] is a chain of
+// selects on scalar conditions and beta's row g a scalar load from the chain's WideParam block (bound by the kernel;
+// indexing a kernel's by-value ChainParam with g would pin all of it to scratch).
+
+// channel ch = g (G + 1) + c -> g, by a multiply and a shift (checked for every channel below)
+template <int G>
+struct ChannelRow {
+    static constexpr uint32_t kShift = 12, kMul = (1u << kShift) / (G + 1) + 1;
+    static constexpr bool exact() {
+        for (uint32_t ch = 0; ch < (uint32_t)(G * G + G); ++ch)
+            if (((ch * kMul) >> kShift) != ch / (G + 1)) return false;
+        return true;
+    }
+    static __device__ __forceinline__ int of(int ch) { return (int)(((uint32_t)ch * kMul) >> kShift); }
+};
+
+// v[g] for a wave-uniform g as selects between the G values.  The values pass through an empty asm first: on plain
+// loads the optimiser folds the chain of selects back into the dynamic index v[g], which keeps the whole state in scratch.
+template <int G>
+__device__ __forceinline__ double pick_group(const double* v, int g) {
+    double r = 0.0;
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+        double vk = v[k];
+        asm("" : "+v"(vk));
+        r = (g == k) ? vk : r;
+    }
+    return r;
+}
+
+// fn(a_i, i) for the G G + G propensities in dict insertion order (s_{g}_{g2} then i_{g}, gillespie_algo.py:180-185)
+template <int G, typename Fn>
+__device__ __forceinline__ void subgroups_each_rate(const WideParam* wp, const double* S, const double* I,
+                                                    double sumN, Fn&& fn) {
+    const double EPIPF_CONSTANT* th = (const double EPIPF_CONSTANT*)wp->theta;
+    const double gamma = th[G * G];
+#pragma unroll 1
+    for (int g = 0; g < G; ++g) {
+        const double Ig = pick_group<G>(I, g);
+        const double EPIPF_CONSTANT* row = th + g * G;
+#pragma unroll
+        for (int g2 = 0; g2 < G; ++g2) fn(((row[g2] * S[g2]) * Ig) / sumN, g * (G + 1) + g2);   // beta[g,g2] s_g2 i_g / sum(N)
+        fn(gamma * Ig, g * (G + 1) + G);                                                       // gamma i_g
+    }
+}
+
+// subgroups_channel_exact in three passes: as = sum(a) (:208), cdf_last, then the count of cdf_i / cdf_last <= u
+template <int G>
+__device__ __forceinline__ int subgroups_channel_exact_wide(const WideParam* wp, const double* S, const double* I,
+                                                            double sumN, double u) {
+    constexpr int NCH = G * G + G;
+    double as = 0.0;
+    subgroups_each_rate<G>(wp, S, I, sumN, [&](double a, int) __attribute__((always_inline)) { as = as + a; });
+    double last = 0.0;
+    subgroups_each_rate<G>(wp, S, I, sumN, [&](double a, int) __attribute__((always_inline)) { last = last + a / as; });
+    double run = 0.0;
+    int ch = 0;
+    subgroups_each_rate<G>(wp, S, I, sumN, [&](double a, int i) __attribute__((always_inline)) {
+        run = run + a / as;
+        ch += (i < NCH - 1 && (run / last) <= u) ? 1 : 0;              // :209-212
+    });
+    return ch;
+}
+
+template <int G>
+struct SubgroupsStateWide {                                            // gillespie_algo.py:148-233
+    static constexpr int NCH = G * G + G;
+    static_assert(ChannelRow<G>::exact(), "channel -> group by multiply and shift");
+    double S[G], I[G], R[G], sumN;
+    const WideParam* wp;                                               // the chain's rates (bind, before load)
+    __device__ __forceinline__ void bind(const WideParam* w) { wp = w; }
+    __device__ __forceinline__ void load(const double* x, const ChainParam&) {
+        sumN = 0.0;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            S[g] = x[3 * g]; I[g] = x[3 * g + 1]; R[g] = x[3 * g + 2];
+            sumN = sumN + ((S[g] + I[g]) + R[g]);                      // sum(N), :176,:182
+        }
+    }
+    // sum(list(evaluated_reactions.values())) (:208) in insertion order; returns 1/sum
+    __device__ __forceinline__ double rates(const ChainParam&) const {
+        double run = 0.0;
+        subgroups_each_rate<G>(wp, S, I, sumN, [&](double a, int) __attribute__((always_inline)) { run = run + a; });
+        return 1.0 / run;
+    }
+    __device__ __forceinline__ bool active() const {                   // :192-193, :222
+        double infected = 0.0;
+#pragma unroll
+        for (int g = 0; g < G; ++g) infected = infected + I[g];
+        return infected > 0.0;
+    }
+    __device__ __forceinline__ bool event(const Block& r, double& t, double tmax, const ChainParam& cp,
+                                          const LogTab* __restrict__ tab) {
+        const double ri = rates(cp);
+        const double tau = ri * neg_log_one_minus_u01(r.x, r.y, tab);  // :207
+        const double u = u01(r.z, r.w);
+        int ch = 0;
+        bool close = false;
+        double run = 0.0;                                              // the cumulative propensities, again
+        subgroups_each_rate<G>(wp, S, I, sumN, [&](double a, int i) __attribute__((always_inline)) {
+            run = run + a;
+            const double q = run * ri;
+            const bool in = i < NCH - 1;
+            ch += (in && q <= u) ? 1 : 0;
+            close |= in && fabs(q - u) <= kBand;
+        });
+        if (close) ch = subgroups_channel_exact_wide<G>(wp, S, I, sumN, u);
+        const double tn = t + tau;
+        if (tn > tmax) return false;                                   // :215-216
+        t = tn;
+        // one group moves: c < G infects group c (s_{g}_{c}, :183), c = G recovers group g (i_{g}, :185)
+        const int g = ChannelRow<G>::of(ch), c = ch - g * (G + 1);
+        const bool inf = c < G;
+        const int q = inf ? c : g;
+#pragma unroll
+        for (int k = 0; k < G; ++k) {
+            const bool hit = q == k;
+            S[k] -= (hit && inf) ? 1.0 : 0.0;
+            I[k] += hit ? (inf ? 1.0 : -1.0) : 0.0;
+            R[k] += (hit && !inf) ? 1.0 : 0.0;
+        }
+        return true;
+    }
+    __device__ __forceinline__ void save(double* x) const {
+#pragma unroll
+        for (int g = 0; g < G; ++g) { x[3 * g] = S[g]; x[3 * g + 1] = I[g]; x[3 * g + 2] = R[g]; }
+    }
+    __device__ __forceinline__ double tau_of(const Block& r, const ChainParam& cp, const LogTab* __restrict__ tab) const {
+        return rates(cp) * neg_log_one_minus_u01(r.x, r.y, tab);
+    }
+};
+template <int G> using SubgroupsStateFor = std::conditional_t<(G > kMaxLaneG), SubgroupsStateWide<G>, SubgroupsState<G>>;
+template <int G> struct SsaState<kSubgroups, G> : SubgroupsStateFor<G> {};
+template <int G> struct SsaState<kSubgroups2, G> : SubgroupsStateFor<G> {};
 
 // ------------------------------------------------------------------------------- certified f32 fast path
 // The exact loop above spends ~45 f64 operations per event (the table log alone ~20, v_rcp_f64 16 cycles).
@@ -915,8 +1075,141 @@ struct FastSubgroupsPacked {                                           // gilles
         return (int)(inf + rec);
     }
 };
-template <int G> struct FastSsa<kSubgroups, G> : FastSubgroups<G> {};
-template <int G> struct FastSsa<kSubgroups2, G> : FastSubgroups<G> {};
+// The subgroup model's f32 state for G > kMaxLaneG (30 to 72 channels): FastSubgroups' arithmetic term for term (the
+// same cum(), so e_as = 4 + NCH and the clock certificate carry over; the band follows e_q), with
+//   - the rates read through the chain's own address at the point of use (scalar loads; 65 of them do not fit the
+//     SGPR file beside the loop's other scalars),
+//   - a per-lane decision: the channel is the count of c_i below the bracket's low side, and the lane is unsure when
+//     the count below its high side differs (the c_i are nondecreasing).  One wave mask per boundary, as the
+//     narrower models keep them, would be 71 SGPR pairs,
+//   - the channel's group from a multiply and a shift (ChannelRow; no 32-bit channel masks).
+// Largest G whose particle-steps take the f32 loop: it stays only where it beat the exact loop on the measured workload
+// (scripts/wide_groups_bench.py, profiles/wide_groups.json: 1.60x at G = 5, 1.18x at G = 6, 0.61x at G = 8, where the
+// kernel holds one wave per SIMD; G = 7 shares G = 8's allocation class and was not measured).  Above it load() returns
+// false -- a constant, so the loop is not compiled in -- and every particle-step runs the exact loop.  Nothing that
+// ships or is tested runs FastSubgroupsWide at G = 7, 8 (its band of 2^-16 for 72 channels included): raising this
+// constant needs the measurement and the fallback tests at that G first.
+constexpr int kWideFastMaxG = 6;
+template <int G>
+struct FastSubgroupsWide {                                             // gillespie_algo.py:148-233
+    static constexpr int NCH = G * G + G;
+    static constexpr bool kWide = true;
+    static constexpr float band() {                                    // (e_q + 2) ulp = (2 (4 + NCH) + 7) ulp, rounded
+        float b = kUlpF;                                               // up to a power of two
+        for (int n = 1; n < 2 * (4 + NCH) + 7; n *= 2) b *= 2.f;
+        return b;
+    }
+    static constexpr float kBand = band();                             // G = 5..7: 2^-17, G = 8: 2^-16
+    static constexpr float kClockT = (float)(NCH + 11) * kUlpF;        // e_as = 4 + NCH
+    static_assert(ChannelRow<G>::exact(), "channel -> group by multiply and shift");
+    double sumN;
+    float S[G], I[G], Ng[G], invN, S0sum, R0sum;
+    const WideParam* wp;                                               // the chain's rates (bind, before load)
+    __device__ __forceinline__ void bind(const WideParam* w) { wp = w; }
+    __device__ __forceinline__ const float EPIPF_CONSTANT* rates() const {   // beta[G][G] then gamma, f32
+        return (const float EPIPF_CONSTANT*)wp->thetaf;
+    }
+    __device__ __forceinline__ bool load(const double* x, const ChainParam&) {
+        if constexpr (G > kWideFastMaxG) return false;                 // the exact loop is faster there (above)
+        sumN = 0.0;
+        bool ok = true;
+        S0sum = 0.f;
+        R0sum = 0.f;
+#pragma unroll
+        for (int q = 0; q < G; ++q) {
+            sumN = sumN + ((x[3 * q] + x[3 * q + 1]) + x[3 * q + 2]);  // sum(N), :176,:182
+            S[q] = (float)x[3 * q];
+            I[q] = (float)x[3 * q + 1];
+            Ng[q] = (S[q] + I[q]) + (float)x[3 * q + 2];
+            S0sum += S[q];
+            R0sum += (float)x[3 * q + 2];
+        }
+        const float EPIPF_CONSTANT* b = rates();
+#pragma unroll 1
+        for (int q = 0; q <= G * G; ++q) ok = ok && rate_ok(b[q]);
+        invN = (float)(1.0 / sumN);
+        return ok && sumN >= 1.0 && sumN < 16777216.0;
+    }
+    __device__ __forceinline__ bool active() const {                   // :192-193, :222
+        float inf = 0.f;
+#pragma unroll
+        for (int q = 0; q < G; ++q) inf += I[q];
+        return inf > 0.f;
+    }
+    // the cumulative rates in channel order (:180-185), one fma per term: fn(c_i, i); returns the total
+    template <typename Fn>
+    __device__ __forceinline__ float scan(float invn, Fn&& fn) const {
+        const float EPIPF_CONSTANT* b = rates();
+        float run = 0.f;
+#pragma unroll
+        for (int q = 0; q < G; ++q) {
+            const float cI = I[q] * invn;
+#pragma unroll
+            for (int q2 = 0; q2 < G; ++q2) {
+                run = fmaf(b[q * G + q2] * S[q2], cI, run);
+                fn(run, q * (G + 1) + q2);
+            }
+            run = fmaf(b[G * G], I[q], run);
+            fn(run, q * (G + 1) + G);
+        }
+        return run;
+    }
+    __device__ __forceinline__ float cum(float* c) const {
+        return scan(invN, [&](float run, int i) __attribute__((always_inline)) { if (i < NCH - 1) c[i] = run; });
+    }
+    // channel = #{i : c_i < Tlo}, certain unless some c_i lies in [Tlo, Thi).  The c_i are recomputed in a second pass
+    // (identical fmas on identical inputs: identical values) instead of kept from cum(): NCH - 1 live VGPRs less in the
+    // loop; the empty asm keeps the compiler from merging the two passes back.
+    __device__ __forceinline__ int decide(float Tlo, float Thi, bool& unsure) const {
+        int lo = 0, hi = 0;
+        float invn = invN;
+        asm volatile("" : "+v"(invn));
+        scan(invn, [&](float run, int i) __attribute__((always_inline)) {
+            if (i < NCH - 1) {
+                lo += (run < Tlo) ? 1 : 0;
+                hi += (run < Thi) ? 1 : 0;
+            }
+        });
+        unsure = lo != hi;
+        return lo;
+    }
+    __device__ __forceinline__ int exact_channel(const ChainParam&, double u) const {
+        double Sd[G], Id[G];
+#pragma unroll
+        for (int q = 0; q < G; ++q) { Sd[q] = (double)S[q]; Id[q] = (double)I[q]; }
+        return subgroups_channel_exact_wide<G>(wp, Sd, Id, sumN, u);
+    }
+    // Channel ch = g (G + 1) + c: c < G is infection s_{g}_{c} (S[c] -> I[c], :183), c = G recovery i_{g} (I[g] -> R,
+    // :185).  One group moves, q = c or g: a select per group, no branch per channel.  s = +1 apply, -1 undo.
+    __device__ __forceinline__ void apply(int ch, float s) {
+        const int g = ChannelRow<G>::of(ch), c = ch - g * (G + 1);
+        const bool inf = c < G;
+        const int q = inf ? c : g;
+        const float dS = inf ? s : 0.f, dI = inf ? s : -s;
+#pragma unroll
+        for (int r = 0; r < G; ++r) {
+            const bool hit = q == r;
+            S[r] -= hit ? dS : 0.f;
+            I[r] += hit ? dI : 0.f;
+        }
+    }
+    __device__ __forceinline__ int save(double* x) const {
+        float inf = S0sum, rec = -R0sum;
+#pragma unroll
+        for (int q = 0; q < G; ++q) {
+            const float R = (Ng[q] - S[q]) - I[q];
+            inf -= S[q];
+            rec += R;
+            x[3 * q] = (double)S[q]; x[3 * q + 1] = (double)I[q]; x[3 * q + 2] = (double)R;
+        }
+        return (int)(inf + rec);
+    }
+};
+template <typename F, typename = void> struct IsWide { static constexpr bool value = false; };
+template <typename F> struct IsWide<F, std::enable_if_t<F::kWide>> { static constexpr bool value = true; };
+template <int G> using FastSubgroupsFor = std::conditional_t<(G > kMaxLaneG), FastSubgroupsWide<G>, FastSubgroups<G>>;
+template <int G> struct FastSsa<kSubgroups, G> : FastSubgroupsFor<G> {};
+template <int G> struct FastSsa<kSubgroups2, G> : FastSubgroupsFor<G> {};
 // the f32 state of the lane-group pass
 template <int MODEL, int G> struct GroupSsa { using type = FastSsa<MODEL, G>; };
 template <int G> struct GroupSsa<kSubgroups, G> { using type = FastSubgroupsPacked<G>; };
@@ -924,14 +1217,17 @@ template <int G> struct GroupSsa<kSubgroups2, G> { using type = FastSubgroupsPac
 
 template <int MODEL, int G>
 __device__ __forceinline__ bool fast_propagate(double* x, const ChainParam& cp, uint32_t j, uint32_t ptag,
-                                               double tmax, int& nev_out, int& iters, bool& eligible) {
+                                               double tmax, int& nev_out, int& iters, bool& eligible,
+                                               const WideParam* wp = nullptr) {   // wp: G > kMaxLaneG only
     using F = FastSsa<MODEL, G>;
     constexpr int NCH = F::NCH;
+    constexpr bool WIDE = IsWide<F>::value;                            // per-lane decision (FastSubgroupsWide)
     iters = 0;
     nev_out = 0;
     eligible = false;
     if (!(cp.flags & kChainFastSsa)) return false;
     F st;
+    if constexpr (WIDE) st.bind(wp);
     if (!st.load(x, cp)) return false;
     eligible = true;
     const float kB = F::kBand * cp.band_slack;                         // the decision band (slack 1: kBand)
@@ -964,6 +1260,13 @@ __device__ __forceinline__ bool fast_propagate(double* x, const ChainParam& cp, 
                 close |= fabsf(q - uc) <= kB;
             }
             if (close) ch = st.exact_channel(cp, u01(r.z, r.w));
+        } else if constexpr (WIDE) {
+            // c_i against the same certified bracket, per lane: a lane with some c_i inside it takes the reference
+            // expression in f64
+            const float Tlo = (uc - kB) * total, Thi = fmaf(2.0f * kB, total, Tlo);
+            bool unsure;
+            ch = st.decide(Tlo, Thi, unsure);
+            if (unsure) ch = st.exact_channel(cp, u01(r.z, r.w));
         } else {
             // c_i against U total as wave masks, the lane-group pass's certified bracket (decide_lo,
             // epipf_group.hpp: Tlo = fl((uc - kBand) total), Thi = fl(Tlo + 2 kBand total)); a lane with some c_i in
@@ -994,13 +1297,13 @@ __device__ __forceinline__ bool fast_propagate(double* x, const ChainParam& cp, 
         df = (float)rem;
         B = fmaf(R, kClockRF, Bt);
         ok = df > B;                                                   // certainly inside the step
-        if constexpr (NCH <= 3) st.apply(ch, 1.f);                     // undone below if the lane overshoots
+        if constexpr (NCH <= 3 || WIDE) st.apply(ch, 1.f);             // undone below if the lane overshoots
         else st.apply_below(below, dS, dI);
         alive = ok && st.active();
     }
     if (!ok) {
         if (!(df < -B)) return false;                                 // boundary too close to call: exact loop
-        if constexpr (NCH <= 3) st.apply(ch, -1.f);                    // the overshooting event is not applied
+        if constexpr (NCH <= 3 || WIDE) st.apply(ch, -1.f);            // the overshooting event is not applied
         else st.undo(dS, dI);
     }
     nev_out = st.save(x);
@@ -1014,8 +1317,10 @@ __device__ __forceinline__ bool fast_propagate(double* x, const ChainParam& cp, 
 // independent dependency chains.  The block drawn after the last event is discarded (one per particle-step).
 template <int MODEL, int G>
 __device__ __forceinline__ int exact_propagate(double* x, const ChainParam& cp, uint32_t j, uint32_t ptag,
-                                               double tmax, const LogTab* __restrict__ tab, int& iters) {
+                                               double tmax, const LogTab* __restrict__ tab, int& iters,
+                                               const WideParam* wp = nullptr) {
     SsaState<MODEL, G> st;
+    if constexpr (G > kMaxLaneG) st.bind(wp);
     st.load(x, cp);
     double t = 0.0;
     uint32_t k = 0;
@@ -1063,6 +1368,10 @@ __device__ __forceinline__ int fast_channel(const F& st, const ChainParam& cp, u
             ch += (q < uc) ? 1 : 0;
             close |= fabsf(q - uc) <= F::kBand * cp.band_slack;
         }
+    } else if constexpr (IsWide<F>::value) {
+        const float kB = F::kBand * cp.band_slack;
+        const float Tlo = (uc - kB) * total, Thi = fmaf(2.0f * kB, total, Tlo);
+        ch = st.decide(Tlo, Thi, close);
     } else {
         const float T = uc * total, band = F::kBand * cp.band_slack * total;
 #pragma unroll
@@ -1097,11 +1406,12 @@ __device__ __forceinline__ void replay_sync() {
 
 template <int MODEL, int G, bool WAVE = false>
 __device__ __forceinline__ int coop_replay(int32_t* row, const ChainParam& cp, uint32_t j, uint32_t ptag, double tmax,
-                                           const LogTab* __restrict__ tab) {
+                                           const LogTab* __restrict__ tab, const WideParam* wp = nullptr) {
     using F = FastSsa<MODEL, G>;
     constexpr int C = (MODEL == kSIR) ? 3 : (MODEL == kSEIR) ? 4 : 3 * G;
     const int lane = (int)(threadIdx.x & 63);
     F st;
+    if constexpr (G > kMaxLaneG) st.bind(wp);
     {
         double x0[C];
 #pragma unroll
@@ -1130,6 +1440,7 @@ __device__ __forceinline__ int coop_replay(int32_t* row, const ChainParam& cp, u
             for (int c = 0; c < C; ++c) xk[c] = (double)row[c];
             mine.save(xk);
             SsaState<MODEL, G> ex;
+            if constexpr (G > kMaxLaneG) ex.bind(wp);
             ex.load(xk, cp);
             tau = ex.tau_of(r, cp, tab);
         }
@@ -1175,17 +1486,18 @@ __device__ __forceinline__ int coop_replay(int32_t* row, const ChainParam& cp, u
 // untouched parent state.
 template <int MODEL, int G>
 __device__ __forceinline__ int ssa_propagate(double* x, const ChainParam& cp, uint32_t j, uint32_t ptag,
-                                             double tmax, const LogTab* __restrict__ tab, int& iters, int& exact) {
+                                             double tmax, const LogTab* __restrict__ tab, int& iters, int& exact,
+                                             const WideParam* wp = nullptr) {
     int fast_iters = 0, fast_nev = 0;
     bool eligible = false;
     exact = 1;
-    if (fast_propagate<MODEL, G>(x, cp, j, ptag, tmax, fast_nev, fast_iters, eligible)) {
+    if (fast_propagate<MODEL, G>(x, cp, j, ptag, tmax, fast_nev, fast_iters, eligible, wp)) {
         iters = fast_iters;
         exact = 0;
         return fast_nev;
     }
     int ex_iters = 0;
-    const int nev = exact_propagate<MODEL, G>(x, cp, j, ptag, tmax, tab, ex_iters);
+    const int nev = exact_propagate<MODEL, G>(x, cp, j, ptag, tmax, tab, ex_iters, wp);
     iters = ex_iters + fast_iters;
     return nev;
 }

@@ -64,8 +64,8 @@ struct StepArgs {
                                    // [2] SSA lane-iterations, [3] wave-iterations x 64, [4] particle-steps on
                                    // the exact SSA loop, [5] waves with one, [6] reference-ambiguous draws
                                    // (summed on the host)
-    double npop[kMaxG], mu[kMaxG], emu[kMaxG];
-    int kmax[kMaxG];
+    double npop[kMaxLaneG], mu[kMaxLaneG], emu[kMaxLaneG];   // groups 0..3 (groups 4..7: WideParam's *_hi fields)
+    int kmax[kMaxLaneG];
     int fused_y, fused_lf;        // one-workgroup filter: Y / the log n! table staged in LDS (epipf_fused.hpp)
     int group_lone;               // lane-group kernel: 1 = its instance without the minimum-waves register bound
                                   // (group_lone_instance, epipf_group.hpp), for launches too small to need the waves
@@ -210,6 +210,10 @@ hipError_t launch_path_sample(const PathArgs& a, hipStream_t s);
 hipError_t launch_simulate(const SimArgs& a, int model, int G, hipStream_t s);
 hipError_t launch_simulate_path(const SimPathArgs& a, int model, int G, hipStream_t s);
 hipError_t launch_resample(const ResampleArgs& a, hipStream_t s);
+// the subgroup models at G = kMaxLaneG + 1 .. kMaxG (epipf_kernels_wide.hip): 64-thread blocks, one lane per particle
+hipError_t launch_filter_wide(const StepArgs& a, int model, int G, int obs, int n_chains, const FilterStreams& fs);
+hipError_t launch_simulate_wide(const SimArgs& a, int G, hipStream_t s);
+hipError_t launch_simulate_path_wide(const SimPathArgs& a, int G, hipStream_t s);
 hipError_t launch_abc_trials(const AbcArgs& a, hipStream_t s, hipStream_t s2, hipEvent_t fork, hipEvent_t join);
 size_t abc_sort_temp_bytes(int n);
 hipError_t launch_abc_select(const AbcSelectArgs& a, hipStream_t s);

@@ -48,6 +48,30 @@ __device__ __forceinline__ void init_particle(const StepArgs& a, const ChainPara
     }
 }
 
+// The same draw for the subgroup models at G > kMaxLaneG: groups 0..3 from the kernel arguments, groups 4..7 from the
+// chain's WideParam block (a function of its own, so that the one above stays the narrower kernels' code as it was).
+template <int MODEL, int G>
+__device__ __forceinline__ void init_particle_wide(const StepArgs& a, const ChainParam& cp, int j, double* x,
+                                                   const WideParam* wp) {
+    static_assert(MODEL >= kSubgroups && G > kMaxLaneG && G <= kMaxG, "the wide subgroup models");
+#pragma unroll
+    for (int c = 0; c < 3 * G; ++c) x[c] = 0.0;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const Block r = philox((uint32_t)g, (uint32_t)j, kDomainInit, cp.f, cp.k0, cp.k1);
+        const double U = u01(r.x, r.y);
+        const bool lo = g < kMaxLaneG;
+        const int h = lo ? 0 : g - kMaxLaneG, gl = lo ? g : 0;
+        const double mu = lo ? a.mu[gl] : wp->mu_hi[h];
+        double pk = lo ? a.emu[gl] : wp->emu_hi[h], F = pk;
+        const int kmax = lo ? a.kmax[gl] : wp->kmax_hi[h];
+        int k = 0;
+        while (U >= F && k < kmax) { k += 1; pk = pk * mu / (double)k; F = F + pk; }
+        x[3 * g] = (lo ? a.npop[gl] : wp->npop_hi[h]) - (double)k;
+        x[3 * g + 1] = (double)k;
+    }
+}
+
 // LDS ordering between the lanes that run a helper: the whole block (__syncthreads), or only the calling wave
 // (WAVE = true: the lane-group kernel runs these on its first wave while the other waves wait at a block barrier).
 template <bool WAVE>

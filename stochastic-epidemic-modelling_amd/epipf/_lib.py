@@ -16,14 +16,14 @@ SIR, SEIR, SIR_SUBGROUPS, SIR_SUBGROUPS2 = 0, 1, 2, 3
 OBS_BINOMIAL, OBS_NORMAL = 0, 1
 RESAMPLE_MULTINOMIAL, RESAMPLE_SYSTEMATIC = 0, 1
 PROFILE_OFF, PROFILE_TIMING, PROFILE_COUNTERS = 0, 1, 2
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 EXPORTS = (
     "epipf_create", "epipf_destroy", "epipf_set_observations", "epipf_set_population", "epipf_run",
     "epipf_run_sampled", "epipf_mh_propose", "epipf_mh_decide", "epipf_mh_peek",
     "epipf_copy_history", "epipf_path_sample", "epipf_simulate", "epipf_resample", "epipf_set_profiling",
     "epipf_get_stats", "epipf_reset_stats", "epipf_set_streams", "epipf_set_lanes", "epipf_last_error", "epipf_abi_version", "epipf_device_count",
-    "epipf_build_id",
+    "epipf_build_id", "epipf_max_groups",
     "epipf_abc", "epipf_abc_trials", "epipf_glibc_log", "epipf_clock_log", "epipf_simulate_path",
 )
 
@@ -106,6 +106,7 @@ def load():
         "epipf_reset_stats": ([P], i32),
         "epipf_last_error": ([], ctypes.c_char_p),
         "epipf_abi_version": ([], i32),
+        "epipf_max_groups": ([], i32),
         "epipf_build_id": ([], ctypes.c_char_p),
         "epipf_device_count": ([], i32),
         "epipf_abc": ([P, P, i32, i32, f64, P, u64, u32, ctypes.c_int64, i32, P, P, P, P], i32),

@@ -45,6 +45,17 @@ def n_compartments(mid, G):
     return 3 if mid == _lib.SIR else 4 if mid == _lib.SEIR else 3 * G
 
 
+def max_groups():
+    """Largest G of the subgroup models (epipf_max_groups)."""
+    return int(_lib.load().epipf_max_groups())
+
+
+def check_groups(mid, G):
+    """The subgroup models' G against the library's limit, before any context is created."""
+    if mid >= _lib.SIR_SUBGROUPS and int(G) > max_groups():
+        raise ValueError(f"subgroup models support at most {max_groups()} groups, got {int(G)}")
+
+
 def theta_vector(mid, theta):
     """Flatten a reference theta: SIR/SEIR arrays, or (beta[G][G], gamma) for the subgroup models
     (pmcmc.py:211-218 passes theta_proposal[0], theta_proposal[1])."""
@@ -53,6 +64,7 @@ def theta_vector(mid, theta):
         beta = np.asarray(beta, dtype=np.float64)
         if beta.ndim != 2 or beta.shape[0] != beta.shape[1]:
             raise ValueError("subgroup theta must be (beta[G][G], gamma)")
+        check_groups(mid, beta.shape[0])
         return np.append(beta.reshape(-1), float(gamma)), beta.shape[0]
     th = np.asarray(theta, dtype=np.float64).reshape(-1)
     need = 2 if mid == _lib.SIR else 3
@@ -66,6 +78,7 @@ class Engine:
         L = _lib.load()
         self.model = model_id(type_model)
         self.G = int(groups) if self.model >= _lib.SIR_SUBGROUPS else 1
+        check_groups(self.model, self.G)
         self.C = n_compartments(self.model, self.G)
         self.K = 3 if self.model == _lib.SIR_SUBGROUPS2 else self.C
         self.N = int(n_particles)
@@ -285,6 +298,7 @@ def get_engine(type_model, groups, n_particles, T, chains=1, device=0):
     (Engine.__del__).  Callers that share a cached engine re-bind their observations / population before each run
     (set_observations / set_population are no-ops when nothing changed)."""
     mid = model_id(type_model)
+    check_groups(mid, groups)
     key = (mid, groups if mid >= _lib.SIR_SUBGROUPS else 1, int(n_particles), int(device))
     eng = _CACHE.get(key)
     if eng is None or eng.t_max < T or eng.max_chains < chains:

@@ -24,7 +24,7 @@ from enum import Enum
 import numpy as np
 
 from . import _lib
-from .engine import get_engine, model_id, n_compartments, theta_vector
+from .engine import check_groups, get_engine, model_id, n_compartments, theta_vector
 
 
 class ModelType(Enum):
@@ -316,6 +316,7 @@ class ChainSampler:
         self.resample = resample
         self.N = int(n_particles)
         G = int(round(math.sqrt(d - (2 if probs is None else 1)))) if mid >= _lib.SIR_SUBGROUPS else 1
+        check_groups(mid, G)
         Y = _check_Y(mid, G, Y)
         T = self.T = Y.shape[0]
         Cc = n_compartments(mid, G)
