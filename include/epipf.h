@@ -14,6 +14,8 @@
  *   epipf_simulate       gillespie_algo.py:10-75 / 78-146 / 148-233  sir_simulate / seir_simulate /
  *                        sir_subgroups_simulate(..., last_values_only=True), batched over states
  *   epipf_simulate_path  the same functions with last_values_only=False (event times + states)
+ *   epipf_forecast       tests/pred_tmps.py:55-64  traj_inf per posterior draw (own theta, own start state), batched:
+ *                        the continuous path over [0, H] binned to one row per day, with ensemble sums and histograms
  *   epipf_resample       pmcmc.py:185-190  normalise + np.random.choice(range(N), N, p=w/sum(w)) with
  *                        caller-supplied uniforms (bit-exact to numpy's legacy choice)
  *   epipf_abc            abc_algo.py:17-109  abc_algo(observed_data, no_of_samples, threshold, priors)
@@ -159,6 +161,25 @@ int epipf_simulate(epipf_ctx* ctx, int n, const int32_t* states_in, const double
 int epipf_simulate_path(epipf_ctx* ctx, int n, const int32_t* states_in, const double* theta, int d,
                         double max_time, uint64_t key, uint32_t filter_index, uint32_t step, int max_events,
                         double* times_out, int32_t* states_out, int32_t* n_events_out, int32_t* final_out);
+
+/* Posterior-predictive forecast: n_draws posterior draws, each with its own parameters theta[i] ([n_draws*d]) and its
+ * own start state states[i] ([n_draws*C]), `replicates` trajectories per draw, all in one launch.  Each trajectory is
+ * the continuous path of epipf_simulate_path over [0, horizon] binned on the device to one row per day: row j
+ * (0..horizon-1) is the state after the last event with time < j + 1, and a day without an event repeats the previous
+ * row (tests/pred_tmps.py:58-63: the last index with floor(time) == j, else the previous row).
+ * Draw i, replicate r draws SSA event k from counter (k, r, step, filter_index + i) (uint32 wrap): its forecast is
+ * epipf_simulate_path of `replicates` copies of states[i] with theta[i] at filter index filter_index + i, bit for bit,
+ * whatever else is in the batch.
+ *   rows_out [n_draws*replicates*horizon*C] int32, or NULL (nothing per trajectory leaves the device)
+ *   sums_out [horizon*C]: sum of every row cell over the n_draws*replicates trajectories (exact)
+ *   hist_out [horizon*C*bins] uint32, or NULL: hist[j][c][v] = trajectories whose row j has value v in compartment c;
+ *            bins must exceed the largest start-state total (every model conserves it)
+ *   events_out (or NULL): accepted events of the whole batch
+ * horizon >= 1, replicates >= 1, n_draws*replicates <= INT32_MAX (< 2^30, and horizon*C <= 65535*64, with rows_out);
+ * n_draws == 0 returns EPIPF_OK with zeros. */
+int epipf_forecast(epipf_ctx* ctx, int n_draws, int replicates, int horizon, const double* theta, int d,
+                   const int32_t* states, uint64_t key, uint32_t filter_index, uint32_t step, int32_t* rows_out,
+                   int64_t* sums_out, uint32_t* hist_out, int bins, int64_t* events_out);
 
 /* Standalone resampler: out[j] = numpy legacy choice(range(n), n, p=w/sum(w)) given uniforms u[j].
  * Returns EPIPF_STATUS_DEGENERATE (as a positive value) where numpy raises ValueError. */

@@ -921,6 +921,97 @@ int epipf_simulate_path(epipf_ctx* c, int n, const int32_t* states_in, const dou
     return EPIPF_OK;
 }
 
+int epipf_forecast(epipf_ctx* c, int n_draws, int replicates, int horizon, const double* theta, int d,
+                   const int32_t* states, uint64_t key, uint32_t filter_index, uint32_t step, int32_t* rows_out,
+                   int64_t* sums_out, uint32_t* hist_out, int bins, int64_t* events_out) {
+    if (!c || !theta || !states || !sums_out) return fail(EPIPF_EINVAL, "NULL argument");
+    if (n_draws < 0) return fail(EPIPF_EINVAL, "n_draws < 0");
+    if (replicates < 1) return fail(EPIPF_EINVAL, "replicates must be >= 1");
+    if (horizon < 1) return fail(EPIPF_EINVAL, "horizon must be >= 1");
+    if (d != theta_dim(c->model, c->G)) return fail(EPIPF_EINVAL, "theta needs %d entries", theta_dim(c->model, c->G));
+    if ((int64_t)n_draws * replicates > INT32_MAX)
+        return fail(EPIPF_EINVAL, "n_draws * replicates must be <= %d", INT32_MAX);
+    const int C = c->C;
+    if ((int64_t)horizon * C > INT32_MAX)
+        return fail(EPIPF_EINVAL, "horizon * %d compartments must be <= %d", C, INT32_MAX);
+    // rows_out: the transpose to the caller's layout runs 64 x 64 tiles on a 2-D grid (launch_forecast_transpose)
+    if (rows_out && ((int64_t)n_draws * replicates >= ((int64_t)1 << 30) || ((int64_t)horizon * C + 63) / 64 > 65535))
+        return fail(EPIPF_EINVAL, "rows_out needs n_draws * replicates < 2^30 and horizon * %d <= %d", C, 65535 * 64);
+    for (size_t i = 0; i < (size_t)n_draws * d; ++i)
+        if (!(theta[i] >= 0.0 && theta[i] < INFINITY))
+            return fail(EPIPF_EINVAL, "theta[%zu][%zu] must be finite and >= 0", i / d, i % d);
+    int64_t largest = 0;
+    for (int i = 0; i < n_draws; ++i) {
+        int64_t total = 0;
+        for (int k = 0; k < C; ++k) {
+            if (states[(size_t)i * C + k] < 0) return fail(EPIPF_EINVAL, "states must be non-negative");
+            total += states[(size_t)i * C + k];
+        }
+        largest = std::max(largest, total);
+    }
+    // a compartment never exceeds its draw's total, which every model conserves: int32 rows, and the histogram's range
+    if (largest > INT32_MAX) return fail(EPIPF_EINVAL, "a draw's state total must be <= %d", INT32_MAX);
+    if (hist_out && (int64_t)bins <= largest)
+        return fail(EPIPF_EINVAL, "bins must be > %lld, the largest state total", (long long)largest);
+    const size_t HC = (size_t)horizon * C;
+    for (size_t i = 0; i < HC; ++i) sums_out[i] = 0;
+    if (events_out) *events_out = 0;
+    if (n_draws == 0) {
+        if (hist_out) memset(hist_out, 0, sizeof(uint32_t) * HC * (size_t)bins);
+        return EPIPF_OK;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const bool wide = c->G > kMaxLaneG;
+    const int n = n_draws * replicates;
+    const size_t pb = align256(cp_slots(c->G, (size_t)n_draws) * sizeof(ChainParam));
+    const size_t sb = align256((size_t)n_draws * C * sizeof(int32_t));
+    const size_t ub = align256((HC + 1) * sizeof(unsigned long long));          // sums, then the event count
+    const size_t hb = hist_out ? align256(HC * (size_t)bins * sizeof(uint32_t)) : 0;
+    const size_t rb = rows_out ? align256(HC * (size_t)n * sizeof(int32_t)) : 0;   // lane-minor, then transposed
+    if (ensure_scratch(c, pb + sb + ub + hb + 2 * rb)) return EPIPF_ENOMEM;
+    char* base = (char*)c->scratch;
+    ChainParam* dcp = (ChainParam*)base;
+    int32_t* din = (int32_t*)(base + pb);
+    unsigned long long* dsums = (unsigned long long*)((char*)din + sb);
+    uint32_t* dhist = hist_out ? (uint32_t*)((char*)dsums + ub) : nullptr;
+    int32_t* drows = rows_out ? (int32_t*)((char*)dsums + ub + hb) : nullptr;
+    // draw i's parameters; its stream is the single-theta calls' at filter index filter_index + i (wrapping)
+    std::vector<ChainParam> hcp(cp_slots(c->G, (size_t)n_draws));
+    memset(hcp.data(), 0, hcp.size() * sizeof(ChainParam));
+    WideParam* hw = wide ? const_cast<WideParam*>(wide_param(hcp.data(), n_draws, 0)) : nullptr;
+    for (int i = 0; i < n_draws; ++i) {
+        ChainParam& q = hcp[i];
+        for (int k = 0; k < d; ++k) set_theta(q, wide ? hw + i : nullptr, k, theta[(size_t)i * d + k]);
+        q.k0 = (uint32_t)key; q.k1 = (uint32_t)(key >> 32); q.f = filter_index + (uint32_t)i;
+        q.clock_slack = 1.f;
+        q.band_slack = 1.f;
+    }
+    HIP_TRY(hipMemcpyAsync(dcp, hcp.data(), hcp.size() * sizeof(ChainParam), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(din, states, sizeof(int32_t) * (size_t)n_draws * C, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(dsums, 0, ub + hb, c->stream));
+    ForecastArgs a{};
+    a.logtab = c->logtab; a.n = n; a.D = n_draws; a.R = replicates; a.H = horizon; a.bins = bins;
+    a.lds_sums = forecast_lds_sums(horizon, C) ? 1 : 0;
+    a.step = step; a.cp = dcp; a.in = din; a.rows = drows; a.sums = dsums; a.hist = dhist; a.events = dsums + HC;
+    hipError_t le = launch_forecast(a, c->model, c->G, c->stream);
+    if (le != hipSuccess) return fail(EPIPF_EHIP, "forecast launch failed: %s", hipGetErrorString(le));
+    std::vector<unsigned long long> hs(HC + 1);
+    HIP_TRY(hipMemcpyAsync(hs.data(), dsums, sizeof(unsigned long long) * (HC + 1), hipMemcpyDeviceToHost, c->stream));
+    if (hist_out)
+        HIP_TRY(hipMemcpyAsync(hist_out, dhist, sizeof(uint32_t) * HC * (size_t)bins, hipMemcpyDeviceToHost, c->stream));
+    if (rows_out) {                                     // lane-minor device rows -> [draw][replicate][day][compartment]
+        int32_t* dout = (int32_t*)((char*)drows + rb);
+        le = launch_forecast_transpose(drows, dout, n, (int)HC, c->stream);
+        if (le != hipSuccess) return fail(EPIPF_EHIP, "forecast transpose launch failed: %s", hipGetErrorString(le));
+        HIP_TRY(hipMemcpyAsync(rows_out, dout, sizeof(int32_t) * HC * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < HC; ++i) sums_out[i] = (int64_t)hs[i];
+    if (events_out) *events_out = (int64_t)hs[HC];
+    trim_scratch(c);
+    return EPIPF_OK;
+}
+
 int epipf_glibc_log(int64_t n, const double* x, double* out) {
     if (n < 0 || (n > 0 && (!x || !out))) return fail(EPIPF_EINVAL, "NULL argument");
     LogTab lt[kLogTabEntries];

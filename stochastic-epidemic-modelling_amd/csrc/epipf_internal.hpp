@@ -107,6 +107,21 @@ struct SimPathArgs {
     int32_t* final_state;        // [n][C]
 };
 
+// posterior-predictive forecast (epipf_forecast, epipf_forecast.hpp): lane j = draw j / R, replicate j % R
+struct ForecastArgs {
+    const LogTab* logtab;
+    int n, D, R, H;              // lanes D R, draws, replicates per draw, days
+    int bins;                    // histogram bins per (day, compartment): values 0..bins-1
+    int lds_sums;                // 1: each block sums its rows in LDS first (forecast_lds_sums)
+    uint32_t step;
+    const ChainParam* cp;        // [D], then D WideParam blocks for G > kMaxLaneG
+    const int32_t* in;           // [D][C] start state of each draw
+    int32_t* rows;               // [H][C][n] lane-minor daily rows, or null
+    unsigned long long* sums;    // [H][C] sum of each row cell over the lanes
+    uint32_t* hist;              // [H][C][bins] count of each row value, or null
+    unsigned long long* events;  // [1] accepted events
+};
+
 struct ResampleArgs {
     int N, B;
     double cert_k;
@@ -214,6 +229,12 @@ hipError_t launch_resample(const ResampleArgs& a, hipStream_t s);
 hipError_t launch_filter_wide(const StepArgs& a, int model, int G, int obs, int n_chains, const FilterStreams& fs);
 hipError_t launch_simulate_wide(const SimArgs& a, int G, hipStream_t s);
 hipError_t launch_simulate_path_wide(const SimPathArgs& a, int G, hipStream_t s);
+// the forecast kernel (epipf_forecast.hip; G = 5..8: epipf_forecast_wide.hip)
+hipError_t launch_forecast(const ForecastArgs& a, int model, int G, hipStream_t s);
+hipError_t launch_forecast_wide(const ForecastArgs& a, int G, hipStream_t s);
+// lane-minor rows [HC][n] -> [n][HC] (HC = H C); hipErrorInvalidValue beyond 65535 x 64 cells per trajectory
+hipError_t launch_forecast_transpose(const int32_t* in, int32_t* out, int n, int HC, hipStream_t s);
+bool forecast_lds_sums(int H, int C);   // the [H][C] block sums fit the launch's dynamic LDS
 hipError_t launch_abc_trials(const AbcArgs& a, hipStream_t s, hipStream_t s2, hipEvent_t fork, hipEvent_t join);
 size_t abc_sort_temp_bytes(int n);
 hipError_t launch_abc_select(const AbcSelectArgs& a, hipStream_t s);

@@ -210,6 +210,24 @@ class Engine:
                 return t[:, :cap], x[:, :cap], nev, fin
             cap = longest
 
+    def forecast(self, thetas, states, horizon, replicates=1, key=0, filter_index=0, step=0, rows=True, bins=0):
+        """epipf_forecast: draw d (thetas[d] flat [D, d], states[d] [D, C]) simulated `replicates` times over
+        [0, horizon] and binned to daily rows.  Returns (rows [D, R, H, C] int32 or None, sums [H, C] int64,
+        hist [H, C, bins] uint32 or None when bins == 0, events)."""
+        thetas = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64))
+        states = np.ascontiguousarray(np.asarray(states, dtype=np.int32).reshape(-1, self.C))
+        D, H, R = states.shape[0], int(horizon), int(replicates)
+        if thetas.ndim != 2 or thetas.shape[0] != D:
+            raise ValueError(f"thetas must be [{D}, d], one row per start state")
+        out = np.empty((D, R, H, self.C), dtype=np.int32) if rows else None
+        sums = np.zeros((H, self.C), dtype=np.int64)
+        hist = np.zeros((H, self.C, int(bins)), dtype=np.uint32) if bins else None
+        ev = np.zeros(1, dtype=np.int64)
+        check(self._L.epipf_forecast(self._h, D, R, H, ptr(thetas), thetas.shape[1], ptr(states),
+                                     int(key) & (2**64 - 1), int(filter_index) & 0xFFFFFFFF, int(step), ptr(out),
+                                     ptr(sums), ptr(hist), int(bins), ptr(ev)), "epipf_forecast")
+        return out, sums, hist, int(ev[0])
+
     def resample(self, w, u):
         w = np.ascontiguousarray(np.asarray(w, dtype=np.float64))
         u = np.ascontiguousarray(np.asarray(u, dtype=np.float64))
