@@ -1215,6 +1215,75 @@ template <int MODEL, int G> struct GroupSsa { using type = FastSsa<MODEL, G>; };
 template <int G> struct GroupSsa<kSubgroups, G> { using type = FastSubgroupsPacked<G>; };
 template <int G> struct GroupSsa<kSubgroups2, G> { using type = FastSubgroupsPacked<G>; };
 
+// The one-lane SIR loop: the generic loop below with the same decisions per lane (channel per event, the step's last
+// event, the hand-back, the saved state) in fewer issue cycles (DESIGN.md §4.2 "The SIR loop's state", §6.2):
+//   state    D = 2S and I instead of S and I: bNh (D I) with bNh = bN/2 is bN (S I) bit for bit (scalings by two
+//            commute with rounding; bN >= 2^-60 keeps bNh and the product normal), and the event is I += s,
+//            D -= 1 + s with s = +1 (infection) or -1 (recovery): 1 + s is 0 or 2, D an even integer below 2^25,
+//            every intermediate exact.  S = D/2 (exact) for exact_channel and save().
+//   channel  s is the sign bit of t = q - uc on 1.0: t < 0 is the generic loop's q < uc, and t = +0 (q == uc; a
+//            difference of floats is zero only then) its infection; inside the band the reference expression
+//            decides, as there, and overwrites s.
+//   exit     df and B are per lane and keep their last values in a lane that has left the loop, so "certainly inside
+//            the step" (df > B) is evaluated once after the loop; a lane that never entered reads as inside.
+__device__ __forceinline__ bool fast_propagate_sir(double* x, const ChainParam& cp, uint32_t j, uint32_t ptag,
+                                                   double tmax, int& nev_out, int& iters, bool& eligible) {
+    using F = FastSsa<kSIR, 1>;
+    F st;
+    if (!st.load(x, cp)) return false;
+    eligible = true;
+    const float kB = F::kBand * cp.band_slack;                         // the decision band (slack 1: kBand)
+    double rem = tmax * kInvLn2;                                       // remaining time, units of 1/ln 2
+    const float Bt = (float)rem * F::kClockT * cp.clock_slack;
+    const float bNh = st.bN * 0.5f, g = st.g;
+    float D = st.S + st.S, I = st.I;
+    float R = 0.f, df = 1.f, B = 0.f, s = 1.f;                         // df > B: a lane that never enters is inside
+    uint32_t ks = 0;                                                   // event index, wave-uniform (SGPR)
+    bool alive = I > 0.f;
+    Block rn{0u, 0u, 0u, 0u};
+    if (alive) rn = philox<true>(0u, j, ptag, cp.f, cp.k0, cp.k1);    // x word inverted: ~x
+    while (alive) {
+        const Block r = rn;
+        ks = __builtin_amdgcn_readfirstlane(ks) + 1u;
+        rn = philox<true>(ks, j, ptag, cp.f, cp.k0, cp.k1);
+        const float c0 = bNh * (D * I);                                // = bN (S I), FastSsa::cum
+        const float total = fmaf(g, I, c0);
+        const float ri = __builtin_amdgcn_rcpf(total);
+        const float uc = __uint_as_float(0x3F800000u | (r.w >> 9)) - (1.0f - kUlpF);   // uf + 2^-24
+        const float t = c0 * ri - uc;
+        s = __builtin_copysignf(1.0f, t);
+        if (fabsf(t) <= kB) {                                          // too close: the reference expression in f64
+            st.S = D * 0.5f;
+            st.I = I;
+            s = st.exact_channel(cp, u01(r.z, r.w)) ? -1.0f : 1.0f;
+        }
+        const uint32_t nh = ~r.y;
+        float lg = __builtin_amdgcn_logf((float)nh * 0x1.0p-32f);     // 1 - U from its top word: <= 2 ulp for x >= 2^-8
+        if (nh < 0x1000000u) {                                         // 1 - U < 2^-8: 0.4% of events
+            if (nh < 4096u) lg = tiny_log2(~r.x, r.y);                // 1 - U < 2^-20
+            else lg = __builtin_amdgcn_logf(fmaf((float)nh, 0x1.0p-32f, (float)r.x * 0x1.0p-64f));  // r.x is ~x
+        }
+        rem = rem + (double)(lg * ri);                                 // np.random.exponential
+        R += ri;
+        I += s;                                                        // undone below if the lane overshoots
+        D -= 1.0f + s;
+        df = (float)rem;
+        B = fmaf(R, kClockRF, Bt);
+        alive = df > B && I > 0.f;
+    }
+    const bool ok = df > B;                                            // certainly inside the step
+    if (!ok) {
+        if (!(df < -B)) return false;                                  // boundary too close to call: exact loop
+        I -= s;                                                        // the overshooting event is not applied
+        D += 1.0f + s;
+    }
+    st.S = D * 0.5f;
+    st.I = I;
+    nev_out = st.save(x);
+    iters = nev_out + (ok ? 0 : 1);
+    return true;
+}
+
 template <int MODEL, int G>
 __device__ __forceinline__ bool fast_propagate(double* x, const ChainParam& cp, uint32_t j, uint32_t ptag,
                                                double tmax, int& nev_out, int& iters, bool& eligible,
@@ -1226,6 +1295,7 @@ __device__ __forceinline__ bool fast_propagate(double* x, const ChainParam& cp, 
     nev_out = 0;
     eligible = false;
     if (!(cp.flags & kChainFastSsa)) return false;
+    if constexpr (MODEL == kSIR && G == 1) return fast_propagate_sir(x, cp, j, ptag, tmax, nev_out, iters, eligible);
     F st;
     if constexpr (WIDE) st.bind(wp);
     if (!st.load(x, cp)) return false;
