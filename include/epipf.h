@@ -22,6 +22,8 @@
  *                        -- the rejection loop batched: one GPU lane per trial, trials accepted in trial order
  *   epipf_abc_trials     abc_algo.py:33-94  one pass of the while-loop body per trial (prior draw, initial
  *                        counts, sir_simulate(..., False), daily table, distance_function) for trials [t0, t0+n)
+ *   epipf_abc_smc_generation / epipf_abc_smc_weights   no reference counterpart: ABC-SMC over the same trials, one
+ *                        generation (proposals from the previous weighted population) and its weight denominators
  *
  * The host wrapper (stochastic-epidemic-modelling_amd/epipf/) binds these with ctypes and keeps
  * the reference's Python signatures.  Conventions:
@@ -205,6 +207,33 @@ int epipf_abc(epipf_ctx* ctx, const double* Y, int T, int no_of_samples, double 
 /* Trials [t0, t0+n): theta_out [n*2]; rows_out [n*T*3] int32 (S, I, R per day) or NULL; dist_out [n] or NULL. */
 int epipf_abc_trials(epipf_ctx* ctx, const double* Y, int T, const double* priors, uint64_t key, uint32_t run_index,
                      uint32_t t0, int n, double* theta_out, int32_t* rows_out, double* dist_out, int64_t* events_out);
+
+/* ABC-SMC (population Monte Carlo ABC with a uniform perturbation kernel) for the SIR model: the
+ * sequential layer over the rejection sampler.  One run keeps one global trial counter t across its generations
+ * (t0 = the trials the earlier generations used); trial t takes its initial counts and SSA events from the counters
+ * above whatever its generation, and its proposal from the domain 6<<24: block (0, t, 6<<24, run) selects the
+ * ancestor, block (1, t, 6<<24, run) perturbs beta (words 0, 1) and gamma (words 2, 3).
+ *
+ * epipf_abc_smc_generation: one generation.  n_prev == 0 is the prior stage: epipf_abc from trial t0 (the same theta,
+ * trajectories and trial count; ancestors -1; prev_* and half_width unused).  n_prev > 0: trial t draws the ancestor
+ * j = min(searchsorted(prev_cdf, u_sel, 'right'), n_prev - 1) (prev_cdf [n_prev]: the previous weights' normalised
+ * cumulative sum, non-decreasing and ending at exactly 1), proposes theta*_c = prev_theta[j][c] + half_width[c] *
+ * (2 u_c - 1), is rejected without simulation (distance +inf) when theta* leaves the prior box lo_c <= theta*_c <=
+ * hi_c, and otherwise runs as an ABC trial with theta = theta*.  The first no_of_samples trials with
+ * distance <= threshold are accepted in trial order: theta_out [n*2], traj_out [n*T*4], dist_out [n] their distances,
+ * ancestor_out [n] their ancestors.  t0 + max_trials <= 2^32; *trials_out counts from t0 by epipf_abc's rule (index
+ * of the last accepted trial - t0 + 1; max_trials when short); batch as epipf_abc.
+ *
+ * epipf_abc_smc_weights: den_out[i] = sum over j, in j order, of prev_w[j] where |theta[i][c] - prev_theta[j][c]| <=
+ * half_width[c] for both c (else +0.0): the denominator of sample i's weight under a uniform prior and kernel,
+ * bit-equal to np.cumsum(np.where(mask, prev_w, 0.0))[-1].  theta [n*2], prev_theta [n_prev*2], prev_w [n_prev]. */
+int epipf_abc_smc_generation(epipf_ctx* ctx, const double* Y, int T, int no_of_samples, double threshold,
+                             const double* priors, const double* prev_theta, const double* prev_cdf, int n_prev,
+                             const double* half_width, uint64_t key, uint32_t run_index, uint32_t t0,
+                             int64_t max_trials, int batch, double* theta_out, double* traj_out, double* dist_out,
+                             int32_t* ancestor_out, int64_t* trials_out, int32_t* accepted_out);
+int epipf_abc_smc_weights(epipf_ctx* ctx, const double* theta, int n, const double* prev_theta, const double* prev_w,
+                          int n_prev, const double* half_width, double* den_out);
 
 /* The device's restatement of glibc's log (the reference's math.log / numpy legacy exponential),
  * evaluated on the host CPU with the same code and table: out[i] = log(x[i]) bit for bit for normal x[i] > 0.

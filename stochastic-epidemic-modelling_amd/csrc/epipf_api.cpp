@@ -1075,6 +1075,11 @@ struct AbcPlan {
     int32_t* count = nullptr;
     double* traj = nullptr;
     double* theta_out = nullptr;
+    double* dist_out = nullptr;       // [samples] accepted distances
+    int32_t* anc_out = nullptr;       // [samples] accepted ancestors
+    int32_t* anc = nullptr;           // [batch] ABC-SMC ancestors of the batch
+    double* prev_theta = nullptr;     // [n_prev][2] ABC-SMC previous population
+    double* prev_cdf = nullptr;       // [n_prev]
 };
 
 // Validates the reference-level arguments and fills the launch constants (abc_algo.py:35-39).
@@ -1122,15 +1127,20 @@ int abc_prepare(epipf_ctx* c, const double* Y, int T, const double* priors, uint
     return 0;
 }
 
-// Carves the ABC buffers for batches of up to `batch` trials and `samples` output slots.
-int abc_buffers(epipf_ctx* c, int T, int batch, int samples, AbcPlan& p) {
+// Carves the ABC buffers for batches of up to `batch` trials and `samples` output slots (n_prev: the previous
+// population of an ABC-SMC generation, else 0).
+int abc_buffers(epipf_ctx* c, int T, int batch, int samples, AbcPlan& p, int n_prev = 0) {
     const size_t b = (size_t)batch;
+    const size_t sz_do = align256(sizeof(double) * (size_t)samples), sz_ao = align256(sizeof(int32_t) * (size_t)samples),
+                 sz_anc = align256(sizeof(int32_t) * b), sz_pt = align256(sizeof(double) * 2 * (size_t)n_prev),
+                 sz_pc = align256(sizeof(double) * (size_t)n_prev);
     const size_t sz_days = align256(sizeof(int32_t) * 3 * (size_t)T * b), sz_theta = align256(sizeof(double) * 2 * b),
                  sz_dist = align256(sizeof(double) * b), sz_Y = align256(sizeof(double) * 3 * (size_t)T),
                  sz_idx = align256(sizeof(int32_t) * (size_t)(samples + 1)), sz_cnt = 256,
                  sz_traj = align256(sizeof(double) * 4 * (size_t)T * samples), sz_to = align256(sizeof(double) * 2 * (size_t)samples);
     const size_t sz_key = align256(sizeof(uint32_t) * b), sz_tmp = align256(abc_sort_temp_bytes(batch));
-    const size_t need = sz_days + sz_theta + sz_dist + sz_Y + sz_idx + sz_cnt + sz_traj + sz_to + 4 * sz_key + sz_tmp;
+    const size_t need = sz_days + sz_theta + sz_dist + sz_Y + sz_idx + sz_cnt + sz_traj + sz_to + 4 * sz_key + sz_tmp +
+                        sz_do + sz_ao + sz_anc + sz_pt + sz_pc;
     if (need > c->abc_bytes) {
         if (c->abc) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->abc); c->abc = nullptr; c->abc_bytes = 0; }
         if (hipMalloc(&c->abc, need) != hipSuccess) return fail(EPIPF_ENOMEM, "ABC buffers hipMalloc(%zu) failed", need);
@@ -1149,8 +1159,13 @@ int abc_buffers(epipf_ctx* c, int T, int batch, int samples, AbcPlan& p) {
         p.args.sort_keys[k] = (uint32_t*)q; q += sz_key;
         p.args.sort_vals[k] = (int32_t*)q; q += sz_key;
     }
-    p.args.sort_temp = q;
+    p.args.sort_temp = q; q += sz_tmp;
     p.args.sort_temp_bytes = sz_tmp;
+    p.dist_out = (double*)q; q += sz_do;
+    p.anc_out = (int32_t*)q; q += sz_ao;
+    p.anc = (int32_t*)q; q += sz_anc;
+    p.prev_theta = (double*)q; q += sz_pt;
+    p.prev_cdf = (double*)q; q += sz_pc;
     p.args.perm = c->abc_order ? p.args.sort_vals[1] : nullptr;
     p.args.Y = p.Ydev;
     return 0;
@@ -1179,6 +1194,17 @@ int abc_launch_trials(epipf_ctx* c, AbcArgs& a0, uint32_t t0, int n) {
     hipError_t le = launch_abc_trials(a, c->stream, a.group_end > 0 ? c->aux[1] : nullptr, c->fork, c->join[1]);
     a.group_lanes = lanes;                                             // automatic again for the next launch
     if (le != hipSuccess) return fail(EPIPF_EHIP, "ABC trial kernel launch failed: %s", hipGetErrorString(le));
+    if (c->profiling) HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    return 0;
+}
+
+// An ABC-SMC batch: every trial on one lane after the sort
+int abc_launch_smc_trials(epipf_ctx* c, AbcArgs& a, const AbcSmcArgs& m, uint32_t t0, int n) {
+    a.t0 = t0;
+    a.n = n;
+    if (c->profiling) HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+    hipError_t le = launch_abc_smc_trials(a, m, c->stream);
+    if (le != hipSuccess) return fail(EPIPF_EHIP, "ABC-SMC trial kernel launch failed: %s", hipGetErrorString(le));
     if (c->profiling) HIP_TRY(hipEventRecord(c->ev[1], c->stream));
     return 0;
 }
@@ -1257,16 +1283,47 @@ int epipf_abc_trials(epipf_ctx* c, const double* Y, int T, const double* priors,
     return EPIPF_OK;
 }
 
-int epipf_abc(epipf_ctx* c, const double* Y, int T, int no_of_samples, double threshold, const double* priors,
-              uint64_t key, uint32_t run_index, int64_t max_trials, int batch, double* theta_out, double* traj_out,
-              int64_t* trials_out, int32_t* accepted_out) {
+namespace {
+// The previous population of an ABC-SMC generation (host pointers; n_prev = 0: the prior stage, none)
+struct AbcSmcPrev {
+    const double* theta;
+    const double* cdf;
+    int n_prev;
+    const double* half_width;
+};
+
+// The accept loop of epipf_abc and of one ABC-SMC generation: trials t0, t0 + 1, ... in batches until no_of_samples
+// are accepted or max_trials have run.  prev.n_prev = 0 draws theta from the prior (the rejection sampler, lane
+// groups and all); otherwise from the previous population (launch_abc_smc_trials).  dist_out / ancestor_out may be
+// NULL.  *trials_out counts from t0.
+int abc_sample(epipf_ctx* c, const double* Y, int T, int no_of_samples, double threshold, const double* priors,
+               const AbcSmcPrev& prev, uint64_t key, uint32_t run_index, uint32_t t0, int64_t max_trials, int batch,
+               double* theta_out, double* traj_out, double* dist_out, int32_t* ancestor_out, int64_t* trials_out,
+               int32_t* accepted_out) {
     AbcPlan p;
     if (int rc = abc_prepare(c, Y, T, priors, key, run_index, p.args)) return rc;
     if (!theta_out || !traj_out || !trials_out || !accepted_out) return fail(EPIPF_EINVAL, "NULL output pointer");
     if (no_of_samples < 0) return fail(EPIPF_EINVAL, "no_of_samples < 0");
     if (std::isnan(threshold)) return fail(EPIPF_EINVAL, "threshold is NaN");
     if (max_trials < 0 || max_trials > (int64_t)(1ull << 32)) return fail(EPIPF_EINVAL, "max_trials must lie in [0, 2^32]");
+    if ((uint64_t)t0 + (uint64_t)max_trials > (1ull << 32))
+        return fail(EPIPF_EINVAL, "t0 + max_trials = %llu exceeds 2^32", (unsigned long long)t0 + (unsigned long long)max_trials);
     if (batch < 0) return fail(EPIPF_EINVAL, "batch < 0");
+    const int n_prev = prev.n_prev;
+    if (n_prev > 0) {
+        if (!prev.theta || !prev.cdf || !prev.half_width) return fail(EPIPF_EINVAL, "NULL previous population");
+        // a proposal outside the prior box has distance +inf, which only a finite threshold rejects
+        if (threshold == INFINITY) return fail(EPIPF_EINVAL, "threshold must be below +inf in an ABC-SMC generation");
+        for (int q = 0; q < 2; ++q)
+            if (!(prev.half_width[q] >= 0.0 && prev.half_width[q] < INFINITY))
+                return fail(EPIPF_EINVAL, "half_width[%d]=%g: kernel half-widths must be finite and >= 0", q, prev.half_width[q]);
+        for (int q = 0; q < 2 * n_prev; ++q)
+            if (!std::isfinite(prev.theta[q])) return fail(EPIPF_EINVAL, "prev_theta[%d][%d] is not finite", q / 2, q % 2);
+        if (!(prev.cdf[0] >= 0.0)) return fail(EPIPF_EINVAL, "prev_cdf[0]=%g: must be >= 0", prev.cdf[0]);
+        for (int q = 1; q < n_prev; ++q)
+            if (!(prev.cdf[q] >= prev.cdf[q - 1])) return fail(EPIPF_EINVAL, "prev_cdf is not non-decreasing at %d", q);
+        if (prev.cdf[n_prev - 1] != 1.0) return fail(EPIPF_EINVAL, "prev_cdf ends at %.17g, not 1", prev.cdf[n_prev - 1]);
+    }
     *trials_out = 0;
     *accepted_out = 0;
     if (no_of_samples == 0) return EPIPF_OK;
@@ -1280,8 +1337,15 @@ int epipf_abc(epipf_ctx* c, const double* Y, int T, int no_of_samples, double th
     const int min_batch = std::min(1 << 18, max_batch);
     int cur = batch > 0 ? std::min(batch, max_batch) : min_batch;
     HIP_TRY(hipSetDevice(c->device));
-    if (int rc = abc_buffers(c, T, max_batch, no_of_samples, p)) return rc;
+    if (int rc = abc_buffers(c, T, max_batch, no_of_samples, p, n_prev)) return rc;
     AbcArgs a = p.args;
+    AbcSmcArgs m{};
+    if (n_prev > 0) {
+        m.prev_theta = p.prev_theta; m.cdf = p.prev_cdf; m.n_prev = n_prev; m.anc = p.anc;
+        for (int q = 0; q < 2; ++q) { m.half[q] = prev.half_width[q]; m.hi[q] = priors[2 * q + 1]; }
+        HIP_TRY(hipMemcpyAsync(p.prev_theta, prev.theta, sizeof(double) * 2 * (size_t)n_prev, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(p.prev_cdf, prev.cdf, sizeof(double) * (size_t)n_prev, hipMemcpyHostToDevice, c->stream));
+    }
     // Early rejection: the device distance is fl(fl(fl(si/T) + fl(sr/T))/2) with si, sr numpy-pairwise
     // sums of the non-negative terms fl(|x_d - y_d|), so it is at least the exact (sum_I + sum_R)/(2T) times
     // (1-u)^(T+4), and a lane's running sum `acc` of the same terms is at most that exact sum times (1+u)^(2T+2)
@@ -1297,7 +1361,11 @@ int epipf_abc(epipf_ctx* c, const double* Y, int T, int no_of_samples, double th
     int32_t* h_cnt = c->h_status;   // pinned staging (>= 1 entry)
     while (have < no_of_samples && t < max_trials) {
         const int nb = (int)std::min<int64_t>(cur, max_trials - t);
-        if (int rc = abc_launch_trials(c, a, (uint32_t)t, nb)) return rc;
+        if (n_prev > 0) {
+            if (int rc = abc_launch_smc_trials(c, a, m, (uint32_t)(t0 + t), nb)) return rc;
+        } else {
+            if (int rc = abc_launch_trials(c, a, (uint32_t)(t0 + t), nb)) return rc;
+        }
         AbcSelectArgs s{};
         s.dist = a.dist; s.n = nb; s.need = no_of_samples - have; s.threshold = threshold; s.idx = p.idx; s.count = p.count;
         hipError_t le = launch_abc_select(s, c->stream);
@@ -1305,6 +1373,7 @@ int epipf_abc(epipf_ctx* c, const double* Y, int T, int no_of_samples, double th
         AbcGatherArgs g{};
         g.days = a.days; g.theta = a.theta; g.idx = p.idx; g.count = p.count; g.n = nb; g.T = T; g.slot0 = have;
         g.traj = p.traj; g.theta_out = p.theta_out;
+        g.dist = a.dist; g.anc = n_prev > 0 ? p.anc : nullptr; g.dist_out = p.dist_out; g.anc_out = p.anc_out;
         le = launch_abc_gather(g, no_of_samples - have, c->stream);
         if (le != hipSuccess) return fail(EPIPF_EHIP, "ABC gather launch failed: %s", hipGetErrorString(le));
         HIP_TRY(hipMemcpyAsync(h_cnt, p.count, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -1327,11 +1396,75 @@ int epipf_abc(epipf_ctx* c, const double* Y, int T, int no_of_samples, double th
     if (have > 0) {
         HIP_TRY(hipMemcpyAsync(theta_out, p.theta_out, sizeof(double) * 2 * (size_t)have, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(traj_out, p.traj, sizeof(double) * 4 * (size_t)T * have, hipMemcpyDeviceToHost, c->stream));
+        if (dist_out)
+            HIP_TRY(hipMemcpyAsync(dist_out, p.dist_out, sizeof(double) * (size_t)have, hipMemcpyDeviceToHost, c->stream));
+        if (ancestor_out)
+            HIP_TRY(hipMemcpyAsync(ancestor_out, p.anc_out, sizeof(int32_t) * (size_t)have, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     if (int rc = abc_read_counters(c)) return rc;
     *accepted_out = have;
     *trials_out = have == no_of_samples ? last + 1 : t;
+    return EPIPF_OK;
+}
+}  // namespace
+
+int epipf_abc(epipf_ctx* c, const double* Y, int T, int no_of_samples, double threshold, const double* priors,
+              uint64_t key, uint32_t run_index, int64_t max_trials, int batch, double* theta_out, double* traj_out,
+              int64_t* trials_out, int32_t* accepted_out) {
+    return abc_sample(c, Y, T, no_of_samples, threshold, priors, AbcSmcPrev{nullptr, nullptr, 0, nullptr}, key,
+                      run_index, 0u, max_trials, batch, theta_out, traj_out, nullptr, nullptr, trials_out, accepted_out);
+}
+
+int epipf_abc_smc_generation(epipf_ctx* c, const double* Y, int T, int no_of_samples, double threshold,
+                             const double* priors, const double* prev_theta, const double* prev_cdf, int n_prev,
+                             const double* half_width, uint64_t key, uint32_t run_index, uint32_t t0,
+                             int64_t max_trials, int batch, double* theta_out, double* traj_out, double* dist_out,
+                             int32_t* ancestor_out, int64_t* trials_out, int32_t* accepted_out) {
+    if (n_prev < 0) return fail(EPIPF_EINVAL, "n_prev < 0");
+    if (!dist_out || !ancestor_out) return fail(EPIPF_EINVAL, "NULL output pointer");
+    return abc_sample(c, Y, T, no_of_samples, threshold, priors, AbcSmcPrev{prev_theta, prev_cdf, n_prev, half_width},
+                      key, run_index, t0, max_trials, batch, theta_out, traj_out, dist_out, ancestor_out, trials_out,
+                      accepted_out);
+}
+
+int epipf_abc_smc_weights(epipf_ctx* c, const double* theta, int n, const double* prev_theta, const double* prev_w,
+                          int n_prev, const double* half_width, double* den_out) {
+    if (!c || !theta || !prev_theta || !prev_w || !half_width || !den_out) return fail(EPIPF_EINVAL, "NULL argument");
+    if (n < 0 || n_prev < 1) return fail(EPIPF_EINVAL, "n=%d, n_prev=%d: need n >= 0 and n_prev >= 1", n, n_prev);
+    for (int q = 0; q < 2; ++q)
+        if (!(half_width[q] >= 0.0 && half_width[q] < INFINITY))
+            return fail(EPIPF_EINVAL, "half_width[%d]=%g: kernel half-widths must be finite and >= 0", q, half_width[q]);
+    for (int q = 0; q < n_prev; ++q)
+        if (!(prev_w[q] >= 0.0 && prev_w[q] < INFINITY))
+            return fail(EPIPF_EINVAL, "prev_w[%d]=%g: weights must be finite and >= 0", q, prev_w[q]);
+    if (n == 0) return EPIPF_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t sz_t = align256(sizeof(double) * 2 * (size_t)n), sz_pt = align256(sizeof(double) * 2 * (size_t)n_prev),
+                 sz_w = align256(sizeof(double) * (size_t)n_prev), sz_d = align256(sizeof(double) * (size_t)n);
+    char* buf = nullptr;
+    if (hipMalloc((void**)&buf, sz_t + sz_pt + sz_w + sz_d) != hipSuccess)
+        return fail(EPIPF_ENOMEM, "ABC-SMC weight buffers hipMalloc(%zu) failed", sz_t + sz_pt + sz_w + sz_d);
+    AbcSmcWeightArgs a{};
+    a.theta = (double*)buf;
+    a.prev_theta = (double*)(buf + sz_t);
+    a.prev_w = (double*)(buf + sz_t + sz_pt);
+    a.den = (double*)(buf + sz_t + sz_pt + sz_w);
+    a.n = n;
+    a.n_prev = n_prev;
+    a.half[0] = half_width[0];
+    a.half[1] = half_width[1];
+    hipError_t e = hipMemcpyAsync((void*)a.theta, theta, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync((void*)a.prev_theta, prev_theta, sizeof(double) * 2 * (size_t)n_prev, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync((void*)a.prev_w, prev_w, sizeof(double) * (size_t)n_prev, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch_abc_smc_weights(a, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(den_out, a.den, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    else (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(buf);
+    if (e != hipSuccess) return fail(EPIPF_EHIP, "ABC-SMC weights: %s", hipGetErrorString(e));
     return EPIPF_OK;
 }
 

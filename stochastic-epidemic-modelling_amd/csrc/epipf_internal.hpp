@@ -180,6 +180,30 @@ struct AbcGatherArgs {
     int n, T, slot0;
     double* traj;                // [samples][T][4]: day, S, I, R (abc_algo.py:56-62 column order)
     double* theta_out;           // [samples][2]
+    const double* dist;          // [n] the batch's distances
+    const int32_t* anc;          // [n] the batch's ancestors (ABC-SMC), or NULL: -1
+    double* dist_out;            // [samples]
+    int32_t* anc_out;            // [samples]
+};
+
+// ABC-SMC: one generation's proposal, theta* = theta_prev[j] + s (2u - 1) with j drawn from the previous
+// weighted population (Philox domain 6 << 24), and the O(n n_prev) weight denominators.
+struct AbcSmcArgs {
+    const double* prev_theta;    // [n_prev][2] previous population (beta, gamma)
+    const double* cdf;           // [n_prev] its normalised cumulative weights (host numpy order)
+    int n_prev;
+    double half[2];              // uniform kernel half-widths
+    double hi[2];                // prior upper bounds (the lower ones: AbcArgs::prior_lo)
+    int32_t* anc;                // [n] the batch's ancestor indices
+};
+
+struct AbcSmcWeightArgs {
+    const double* theta;         // [n][2] new samples
+    const double* prev_theta;    // [n_prev][2]
+    const double* prev_w;        // [n_prev]
+    int n, n_prev;
+    double half[2];
+    double* den;                 // [n] sum of prev_w over the previous points within the kernel, in j order
 };
 
 // Streams of one filter run: group g of the chains runs on s[g]; s[0] is the context stream, the others have
@@ -239,5 +263,10 @@ hipError_t launch_abc_trials(const AbcArgs& a, hipStream_t s, hipStream_t s2, hi
 size_t abc_sort_temp_bytes(int n);
 hipError_t launch_abc_select(const AbcSelectArgs& a, hipStream_t s);
 hipError_t launch_abc_gather(const AbcGatherArgs& a, int max_count, hipStream_t s);
+hipError_t launch_abc_sort(const AbcArgs& a, hipStream_t s);       // sort_keys/vals[0] -> [1], longest first
+hipError_t launch_abc_distance(const AbcArgs& a, hipStream_t s);
+// abc_smc_kernels.hip: proposal (+ predicted lengths), sort, the one-lane trial kernel in SMC mode, distances
+hipError_t launch_abc_smc_trials(const AbcArgs& a, const AbcSmcArgs& m, hipStream_t s);
+hipError_t launch_abc_smc_weights(const AbcSmcWeightArgs& a, hipStream_t s);
 
 }  // namespace epipf

@@ -9,10 +9,10 @@ from .pmcmc import (ModelType, chain_key, particle_filter, particle_mcmc, partic
                     particle_path_sampler, seed_stream)
 from .gillespie import (sir_simulate, seir_simulate, sir_subgroups_simulate, simulate_batch,  # noqa: F401
                         simulate_path_batch)
-from .abc import abc_algo, abc_run  # noqa: F401
+from .abc import abc_algo, abc_run, abc_smc  # noqa: F401
 from .forecast import forecast, forecast_from_chain  # noqa: F401
 
 __all__ = ["Engine", "get_engine", "ModelType", "particle_filter", "particle_mcmc", "particle_mcmc_chains",
            "particle_path_sampler", "seed_stream", "chain_key", "sir_simulate", "seir_simulate",
-           "sir_subgroups_simulate", "simulate_batch", "simulate_path_batch", "abc_algo", "abc_run", "forecast",
+           "sir_subgroups_simulate", "simulate_batch", "simulate_path_batch", "abc_algo", "abc_run", "abc_smc", "forecast",
            "forecast_from_chain"]

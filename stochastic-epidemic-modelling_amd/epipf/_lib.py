@@ -25,7 +25,7 @@ EXPORTS = (
     "epipf_get_stats", "epipf_reset_stats", "epipf_set_streams", "epipf_set_lanes", "epipf_last_error", "epipf_abi_version", "epipf_device_count",
     "epipf_build_id", "epipf_max_groups",
     "epipf_abc", "epipf_abc_trials", "epipf_glibc_log", "epipf_clock_log", "epipf_simulate_path",
-    "epipf_forecast",
+    "epipf_forecast", "epipf_abc_smc_generation", "epipf_abc_smc_weights",
 )
 
 
@@ -116,6 +116,9 @@ def load():
         "epipf_clock_log": ([ctypes.c_int64, P, P], i32),
         "epipf_simulate_path": ([P, i32, P, P, i32, f64, u64, u32, u32, i32, P, P, P, P], i32),
         "epipf_forecast": ([P, i32, i32, i32, P, i32, P, u64, u32, u32, P, P, P, i32, P], i32),
+        "epipf_abc_smc_generation": ([P, P, i32, i32, f64, P, P, P, i32, P, u64, u32, u32, ctypes.c_int64, i32,
+                                      P, P, P, P, P, P], i32),
+        "epipf_abc_smc_weights": ([P, P, i32, P, P, i32, P, P], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -272,6 +272,50 @@ class Engine:
         a = int(acc[0])
         return theta[:a], traj[:a], int(trials[0]), a
 
+    def abc_smc_generation(self, observed_data, no_of_samples, threshold, priors, prev_theta=None, prev_cdf=None,
+                           half_width=None, key=0, run_index=0, t0=0, max_trials=None, batch=0):
+        """One ABC-SMC generation (epipf_abc_smc_generation): (theta [n,2], trajectories [n,T,4], distances [n],
+        ancestors [n] int32, trials, accepted).  prev_theta None or empty: the prior stage.  max_trials None: every
+        trial index left from t0 (2^32 - t0)."""
+        Y, pr = self._abc_inputs(observed_data, priors)
+        if max_trials is None:
+            max_trials = 2**32 - int(t0)
+        n = int(no_of_samples)
+        n_prev = 0 if prev_theta is None else len(prev_theta)
+        pt = pc = hw = None
+        if n_prev:
+            pt = np.ascontiguousarray(np.asarray(prev_theta, dtype=np.float64).reshape(n_prev, 2))
+            pc = np.ascontiguousarray(np.asarray(prev_cdf, dtype=np.float64).reshape(-1))
+            hw = np.ascontiguousarray(np.asarray(half_width, dtype=np.float64).reshape(-1))
+            if pc.shape[0] != n_prev or hw.shape[0] != 2:
+                raise ValueError("prev_cdf must be [n_prev] and half_width [2]")
+        theta = np.empty((max(n, 1), 2))
+        traj = np.empty((max(n, 1), Y.shape[0], 4))
+        dist = np.empty(max(n, 1))
+        anc = np.empty(max(n, 1), dtype=np.int32)
+        trials = np.zeros(1, dtype=np.int64)
+        acc = np.zeros(1, dtype=np.int32)
+        check(self._L.epipf_abc_smc_generation(self._h, ptr(Y), Y.shape[0], n, float(threshold), ptr(pr), ptr(pt),
+                                               ptr(pc), n_prev, ptr(hw), int(key) & (2**64 - 1),
+                                               int(run_index) & 0xFFFFFFFF, int(t0), int(max_trials), int(batch),
+                                               ptr(theta), ptr(traj), ptr(dist), ptr(anc), ptr(trials), ptr(acc)),
+              "epipf_abc_smc_generation")
+        a = int(acc[0])
+        return theta[:a], traj[:a], dist[:a], anc[:a], int(trials[0]), a
+
+    def abc_smc_weights(self, theta, prev_theta, prev_w, half_width):
+        """Weight denominators of new samples theta [n,2] against the previous population (epipf_abc_smc_weights)."""
+        th = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).reshape(-1, 2))
+        pt = np.ascontiguousarray(np.asarray(prev_theta, dtype=np.float64).reshape(-1, 2))
+        pw = np.ascontiguousarray(np.asarray(prev_w, dtype=np.float64).reshape(-1))
+        hw = np.ascontiguousarray(np.asarray(half_width, dtype=np.float64).reshape(-1))
+        if pw.shape[0] != pt.shape[0] or hw.shape[0] != 2:
+            raise ValueError("prev_w must be [n_prev] and half_width [2]")
+        den = np.empty(th.shape[0])
+        check(self._L.epipf_abc_smc_weights(self._h, ptr(th), th.shape[0], ptr(pt), ptr(pw), pt.shape[0], ptr(hw),
+                                            ptr(den)), "epipf_abc_smc_weights")
+        return den
+
     # ------------------------------------------------------------------ stats
     def set_profiling(self, level=_lib.PROFILE_COUNTERS):
         """level: PROFILE_OFF / PROFILE_TIMING (HIP events only, kernels unchanged) / PROFILE_COUNTERS
