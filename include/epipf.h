@@ -16,6 +16,8 @@
  *   epipf_simulate_path  the same functions with last_values_only=False (event times + states)
  *   epipf_forecast       tests/pred_tmps.py:55-64  traj_inf per posterior draw (own theta, own start state), batched:
  *                        the continuous path over [0, H] binned to one row per day, with ensemble sums and histograms
+ *   epipf_smooth / epipf_smooth_history   no reference counterpart: the smoothing distribution over the observed window
+ *                        (daily means, quantiles, surviving lineages) from the resident history, or from a caller's
  *   epipf_resample       pmcmc.py:185-190  normalise + np.random.choice(range(N), N, p=w/sum(w)) with
  *                        caller-supplied uniforms (bit-exact to numpy's legacy choice)
  *   epipf_abc            abc_algo.py:17-109  abc_algo(observed_data, no_of_samples, threshold, priors)
@@ -182,6 +184,34 @@ int epipf_simulate_path(epipf_ctx* ctx, int n, const int32_t* states_in, const d
 int epipf_forecast(epipf_ctx* ctx, int n_draws, int replicates, int horizon, const double* theta, int d,
                    const int32_t* states, uint64_t key, uint32_t filter_index, uint32_t step, int32_t* rows_out,
                    int64_t* sums_out, uint32_t* hist_out, int bins, int64_t* events_out);
+
+/* Particle smoother: daily state estimates over the observed window from a filter's whole history
+ * h[T][N][C] (hidden), a[T][N] (ancestry), as a backward pass of integer multiplicities.  With shift = `lineage`:
+ *   m[T-1][i] = 1;  m[p][i] = sum of m[p+1][j] over the j with a[p+shift][j] == i  (p = T-2 .. 0)
+ *   sums[p][c] = sum_i m[p][i] h[p][i][c]  (exact);  lineages[p] = #{i : m[p][i] > 0}
+ *   quantile q of cell (p, c) = the smallest v with sum of m[p][i] over h[p][i][c] <= v  >=  max(ceil(q N), 1)
+ *                               (np.quantile(..., method="inverted_cdf") over the N lineages; `bins` when values >= bins,
+ *                               which are not counted, keep the counts below the rank)
+ * EPIPF_LINEAGE_REFERENCE follows a[p] as particle_path_sampler does (pmcmc.py:236-248): every output is the statistic
+ * over the N trajectories that sampler returns for chosen = 0..N-1.  EPIPF_LINEAGE_GENEALOGY follows a[p+1], the parent
+ * of a day-(p+1) particle: the true ancestral tree.  EPIPF_SMOOTH_PREDICTIVE sets m = 1 on every day (the particle cloud
+ * itself; lineages = N).  The mean is sums / N.
+ *   q [n_q] in [0, 1]; n_q == 0: no histogram is built (quant_out may be NULL, bins is ignored)
+ *   sums_out [n*T*C]; quant_out [n*n_q*T*C]; lineages_out [n*T]
+ * epipf_smooth: the first n_chains chains of the last run (EPIPF_ESTATE before any); a chain whose last status was not
+ * EPIPF_STATUS_OK gets zeros and its history is not walked.  epipf_smooth_history: the same kernels on host arrays
+ * hidden [n*T*N*C] (>= 0) and ancestry [n*T*N] (in [0, N)); any context works, its model and N are ignored.
+ * The histograms (T*C*bins*4 bytes per chain, at most 256 MiB) stay on the device; chains are processed in slices when
+ * together they exceed the call's scratch budget.  T == 1 is valid; C <= 64. */
+#define EPIPF_LINEAGE_REFERENCE 0
+#define EPIPF_LINEAGE_GENEALOGY 1
+#define EPIPF_SMOOTH_SMOOTHING 0
+#define EPIPF_SMOOTH_PREDICTIVE 1
+int epipf_smooth(epipf_ctx* ctx, int n_chains, int lineage, int kind, const double* q, int n_q, int bins,
+                 int64_t* sums_out, int32_t* quant_out, int32_t* lineages_out);
+int epipf_smooth_history(epipf_ctx* ctx, int n, int T, int N, int C, const int32_t* hidden, const int32_t* ancestry,
+                         int lineage, int kind, const double* q, int n_q, int bins, int64_t* sums_out,
+                         int32_t* quant_out, int32_t* lineages_out);
 
 /* Standalone resampler: out[j] = numpy legacy choice(range(n), n, p=w/sum(w)) given uniforms u[j].
  * Returns EPIPF_STATUS_DEGENERATE (as a positive value) where numpy raises ValueError. */

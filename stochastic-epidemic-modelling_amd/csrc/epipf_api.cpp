@@ -21,6 +21,7 @@
 #include "../../include/epipf.h"
 #include "abc_device.hpp"
 #include "epipf_internal.hpp"
+#include "epipf_smooth.hpp"
 
 using namespace epipf;
 
@@ -1010,6 +1011,127 @@ int epipf_forecast(epipf_ctx* c, int n_draws, int replicates, int horizon, const
     if (events_out) *events_out = (int64_t)hs[HC];
     trim_scratch(c);
     return EPIPF_OK;
+}
+
+// ------------------------------------------------------------------------------- particle smoother
+// One chain's histogram above this is refused (as epipf.forecast refuses its own); the chains of a call share at most
+// kSmoothScratch of histogram and global multiplicity rows, in slices (EPIPF_SMOOTH_SCRATCH_MB overrides, for tests).
+constexpr size_t kSmoothHistLimit = (size_t)256 << 20;
+constexpr size_t kSmoothScratch = (size_t)4 << 30;
+
+// The smoother over n chains of [T][N][C] histories: the context's own (up_hidden == NULL: its strides and the last
+// run's status) or the caller's host arrays, uploaded to scratch.
+static int smooth_run(epipf_ctx* c, int n, int T, int N, int C, const int32_t* up_hidden, const int32_t* up_ancestry,
+                      int lineage, int kind, const double* q, int n_q, int bins, int64_t* sums_out, int32_t* quant_out,
+                      int32_t* lineages_out) {
+    if (!sums_out || !lineages_out) return fail(EPIPF_EINVAL, "NULL argument");
+    if (lineage != EPIPF_LINEAGE_REFERENCE && lineage != EPIPF_LINEAGE_GENEALOGY)
+        return fail(EPIPF_EINVAL, "unknown lineage %d", lineage);
+    if (kind != EPIPF_SMOOTH_SMOOTHING && kind != EPIPF_SMOOTH_PREDICTIVE) return fail(EPIPF_EINVAL, "unknown kind %d", kind);
+    if (n_q < 0 || (n_q > 0 && !q)) return fail(EPIPF_EINVAL, "n_q=%d needs q", n_q);
+    if (n_q > 0 && (bins < 1 || !quant_out)) return fail(EPIPF_EINVAL, "quantiles need bins >= 1 and quant_out");
+    for (int i = 0; i < n_q; ++i)
+        if (!(q[i] >= 0.0 && q[i] <= 1.0)) return fail(EPIPF_EINVAL, "q[%d] must lie in [0, 1]", i);
+    if (C > kSmoothMaxC) return fail(EPIPF_EINVAL, "at most %d compartments, got %d", kSmoothMaxC, C);
+    if (N > kSmoothMaxN) return fail(EPIPF_EINVAL, "at most %d particles, got %d", kSmoothMaxN, N);
+    const size_t TC = (size_t)T * C;
+    const size_t hb1 = n_q > 0 ? TC * (size_t)bins * sizeof(uint32_t) : 0;   // one chain's histogram
+    if (hb1 > kSmoothHistLimit)
+        return fail(EPIPF_EINVAL, "the quantile histogram needs %zu bytes (> %zu): call with no quantiles and reduce the "
+                    "history instead", hb1, kSmoothHistLimit);
+    const bool predictive = kind == EPIPF_SMOOTH_PREDICTIVE;
+    bool lds_rows = N <= kSmoothLdsMaxN;
+    if (const char* e = getenv("EPIPF_SMOOTH_LDS")) lds_rows = lds_rows && atoi(e) != 0;
+    const size_t mb1 = (predictive || lds_rows) ? 0 : 2 * sizeof(uint32_t) * (size_t)N;   // one chain's global rows
+    size_t budget = kSmoothScratch;
+    if (const char* e = getenv("EPIPF_SMOOTH_SCRATCH_MB")) budget = (size_t)std::max(1, atoi(e)) << 20;
+    // chains per slice: what the budget holds, at least one (one chain's histogram is within kSmoothHistLimit)
+    int slice = n;
+    if (hb1 + mb1 > 0) slice = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, budget / (hb1 + mb1)));
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t ob_s = align256((size_t)n * TC * sizeof(unsigned long long));
+    const size_t ob_l = align256((size_t)n * T * sizeof(int32_t));
+    const size_t ob_q = n_q > 0 ? align256((size_t)n * n_q * TC * sizeof(int32_t)) : 0;
+    const size_t ob_r = n_q > 0 ? align256((size_t)n_q * sizeof(uint32_t)) : 0;
+    const size_t sb_h = align256((size_t)slice * hb1), sb_m = align256((size_t)slice * mb1);
+    const size_t ub_h = up_hidden ? align256((size_t)n * T * N * C * sizeof(int32_t)) : 0;
+    const size_t ub_a = up_hidden ? align256((size_t)n * T * N * sizeof(int32_t)) : 0;
+    if (ensure_scratch(c, ob_s + ob_l + ob_q + ob_r + sb_h + sb_m + ub_h + ub_a)) return EPIPF_ENOMEM;
+    char* p = (char*)c->scratch;
+    unsigned long long* dsums = (unsigned long long*)p; p += ob_s;
+    int32_t* dlin = (int32_t*)p; p += ob_l;
+    int32_t* dquant = (int32_t*)p; p += ob_q;
+    uint32_t* dranks = (uint32_t*)p; p += ob_r;
+    uint32_t* dhist = (uint32_t*)p; p += sb_h;
+    uint32_t* drows = (uint32_t*)p; p += sb_m;
+    int32_t* dhid = (int32_t*)p; p += ub_h;
+    int32_t* danc = (int32_t*)p;
+    HIP_TRY(hipMemsetAsync(dsums, 0, ob_s + ob_l + ob_q, c->stream));
+    std::vector<uint32_t> ranks((size_t)n_q);
+    uint32_t max_rank = 0;
+    for (int i = 0; i < n_q; ++i) {                      // numpy's inverted_cdf rule, q N in float64
+        ranks[i] = (uint32_t)std::max(std::ceil(q[i] * (double)N), 1.0);
+        max_rank = std::max(max_rank, ranks[i]);
+    }
+    if (n_q > 0) HIP_TRY(hipMemcpyAsync(dranks, ranks.data(), sizeof(uint32_t) * n_q, hipMemcpyHostToDevice, c->stream));
+    SmoothArgs a{};
+    a.T = T; a.N = N; a.C = C; a.shift = lineage == EPIPF_LINEAGE_GENEALOGY ? 1 : 0; a.predictive = predictive ? 1 : 0;
+    a.bins = bins; a.sums = dsums; a.lineages = dlin;
+    if (up_hidden) {
+        HIP_TRY(hipMemcpyAsync(dhid, up_hidden, sizeof(int32_t) * (size_t)n * T * N * C, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(danc, up_ancestry, sizeof(int32_t) * (size_t)n * T * N, hipMemcpyHostToDevice, c->stream));
+        a.hidden = dhid; a.ancestry = danc; a.status = nullptr;
+        a.hist_stride = (size_t)T * N * C; a.anc_stride = (size_t)T * N;
+    } else {
+        a.hidden = c->hidden; a.ancestry = c->ancestry; a.status = c->status;
+        a.hist_stride = c->hist_stride; a.anc_stride = c->anc_stride;
+    }
+    for (int c0 = 0; c0 < n; c0 += slice) {
+        const int k = std::min(slice, n - c0);
+        a.n = k; a.chain0 = c0;
+        a.mrows = mb1 ? drows : nullptr;
+        a.hist = hb1 ? dhist : nullptr;
+        if (hb1) HIP_TRY(hipMemsetAsync(dhist, 0, (size_t)k * hb1, c->stream));
+        hipError_t le = launch_smooth(a, c->stream);
+        if (le != hipSuccess) return fail(EPIPF_EHIP, "smooth launch failed: %s", hipGetErrorString(le));
+        if (n_q > 0) {
+            SmoothQuantArgs qa{};
+            qa.n = k; qa.chain0 = c0; qa.T = T; qa.C = C; qa.bins = bins; qa.n_q = n_q; qa.max_rank = max_rank;
+            qa.status = a.status; qa.hist = dhist; qa.ranks = dranks; qa.quant = dquant;
+            le = launch_smooth_quantiles(qa, c->stream);
+            if (le != hipSuccess) return fail(EPIPF_EHIP, "smooth quantile launch failed: %s", hipGetErrorString(le));
+        }
+    }
+    static_assert(sizeof(int64_t) == sizeof(unsigned long long), "sums are copied out as they are");
+    HIP_TRY(hipMemcpyAsync(sums_out, dsums, sizeof(int64_t) * (size_t)n * TC, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(lineages_out, dlin, sizeof(int32_t) * (size_t)n * T, hipMemcpyDeviceToHost, c->stream));
+    if (n_q > 0)
+        HIP_TRY(hipMemcpyAsync(quant_out, dquant, sizeof(int32_t) * (size_t)n * n_q * TC, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    trim_scratch(c);
+    return EPIPF_OK;
+}
+
+int epipf_smooth(epipf_ctx* c, int n_chains, int lineage, int kind, const double* q, int n_q, int bins,
+                 int64_t* sums_out, int32_t* quant_out, int32_t* lineages_out) {
+    if (!c) return fail(EPIPF_EINVAL, "NULL context");
+    if (!c->have_run) return fail(EPIPF_ESTATE, "no filter has run on this context");
+    if (n_chains < 1 || n_chains > c->last_chains) return fail(EPIPF_EINVAL, "n_chains=%d outside [1, %d]", n_chains, c->last_chains);
+    return smooth_run(c, n_chains, c->last_T, c->N, c->C, nullptr, nullptr, lineage, kind, q, n_q, bins, sums_out,
+                      quant_out, lineages_out);
+}
+
+int epipf_smooth_history(epipf_ctx* c, int n, int T, int N, int C, const int32_t* hidden, const int32_t* ancestry,
+                         int lineage, int kind, const double* q, int n_q, int bins, int64_t* sums_out,
+                         int32_t* quant_out, int32_t* lineages_out) {
+    if (!c || !hidden || !ancestry) return fail(EPIPF_EINVAL, "NULL argument");
+    if (n < 1 || T < 1 || N < 1 || C < 1) return fail(EPIPF_EINVAL, "n, T, N, C must be >= 1");
+    if ((double)n * T * N * C > (double)((size_t)1 << 40)) return fail(EPIPF_EINVAL, "history too large");
+    for (size_t i = 0; i < (size_t)n * T * N * C; ++i)
+        if (hidden[i] < 0) return fail(EPIPF_EINVAL, "counts must be non-negative");
+    for (size_t i = 0; i < (size_t)n * T * N; ++i)
+        if (ancestry[i] < 0 || ancestry[i] >= N) return fail(EPIPF_EINVAL, "ancestors must lie in [0, N)");
+    return smooth_run(c, n, T, N, C, hidden, ancestry, lineage, kind, q, n_q, bins, sums_out, quant_out, lineages_out);
 }
 
 int epipf_glibc_log(int64_t n, const double* x, double* out) {

@@ -16,6 +16,8 @@ SIR, SEIR, SIR_SUBGROUPS, SIR_SUBGROUPS2 = 0, 1, 2, 3
 OBS_BINOMIAL, OBS_NORMAL = 0, 1
 RESAMPLE_MULTINOMIAL, RESAMPLE_SYSTEMATIC = 0, 1
 PROFILE_OFF, PROFILE_TIMING, PROFILE_COUNTERS = 0, 1, 2
+LINEAGE_REFERENCE, LINEAGE_GENEALOGY = 0, 1
+SMOOTH_SMOOTHING, SMOOTH_PREDICTIVE = 0, 1
 ABI_VERSION = 9
 
 EXPORTS = (
@@ -25,7 +27,7 @@ EXPORTS = (
     "epipf_get_stats", "epipf_reset_stats", "epipf_set_streams", "epipf_set_lanes", "epipf_last_error", "epipf_abi_version", "epipf_device_count",
     "epipf_build_id", "epipf_max_groups",
     "epipf_abc", "epipf_abc_trials", "epipf_glibc_log", "epipf_clock_log", "epipf_simulate_path",
-    "epipf_forecast", "epipf_abc_smc_generation", "epipf_abc_smc_weights",
+    "epipf_forecast", "epipf_abc_smc_generation", "epipf_abc_smc_weights", "epipf_smooth", "epipf_smooth_history",
 )
 
 
@@ -119,6 +121,8 @@ def load():
         "epipf_abc_smc_generation": ([P, P, i32, i32, f64, P, P, P, i32, P, u64, u32, u32, ctypes.c_int64, i32,
                                       P, P, P, P, P, P], i32),
         "epipf_abc_smc_weights": ([P, P, i32, P, P, i32, P, P], i32),
+        "epipf_smooth": ([P, i32, i32, i32, P, i32, i32, P, P, P], i32),
+        "epipf_smooth_history": ([P, i32, i32, i32, i32, P, P, i32, i32, P, i32, i32, P, P, P], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

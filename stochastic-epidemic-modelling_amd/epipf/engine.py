@@ -94,6 +94,7 @@ class Engine:
         self._pop = None
         self.bound_to = None                             # token of the ChainSampler whose data is loaded (_bind)
         self.T = 0
+        self._last_n = None
 
     # ------------------------------------------------------------------ lifecycle
     def close(self):
@@ -159,6 +160,7 @@ class Engine:
                                             ptr(fidx), ptr(act), mode, ptr(ch), ptr(lz), ptr(st), ptr(tr)),
                   "epipf_run_sampled")
         self._last_n = n
+        self._last_status = st.copy()                    # Engine.smooth: rows of chains that did not run are NaN
         _PARTICLE_STEPS[0] += (n if act is None else int(np.count_nonzero(act))) * self.N * self.T
         return (lz, st) if chosen is None else (lz, st, tr)
 
@@ -227,6 +229,45 @@ class Engine:
                                      int(key) & (2**64 - 1), int(filter_index) & 0xFFFFFFFF, int(step), ptr(out),
                                      ptr(sums), ptr(hist), int(bins), ptr(ev)), "epipf_forecast")
         return out, sums, hist, int(ev[0])
+
+    def smooth(self, n_chains=None, quantiles=(0.05, 0.5, 0.95), lineage="genealogy", kind="smoothing", bins=None):
+        """Daily means, quantiles and surviving-lineage counts of the last run's first n_chains chains, from the history
+        resident on the device (epipf_smooth; epipf.smoothing has the definition).  Returns Smoothed with a leading
+        chain axis: mean [n, T, C], quantiles [n, Q, T, C] or None, lineages [n, T], sums [n, T, C], zetas None.  Rows
+        of chains whose last status was not OK are NaN in mean and 0 elsewhere.  bins defaults to the population total
+        + 1 (every model conserves it)."""
+        from . import smoothing
+        lin, knd, q = smoothing.check_options(lineage, kind, quantiles)
+        n = int(n_chains) if n_chains is not None else self._last_n or 1   # before any run: the library's EPIPF_ESTATE
+        if bins is None:
+            if self._pop is None:
+                raise ValueError("bins=None needs set_population")
+            bins = int(sum(self._pop[0])) + 1
+        nq = 0 if q is None else q.size
+        rows = max(n, 1)                                  # a bad n_chains is the library's EPIPF_EINVAL
+        sums = np.zeros((rows, self.T, self.C), dtype=np.int64)
+        lineages = np.zeros((rows, self.T), dtype=np.int32)
+        quant = np.zeros((rows, nq, self.T, self.C), dtype=np.int32) if nq else None
+        check(self._L.epipf_smooth(self._h, n, lin, knd, ptr(q), nq, int(bins) if nq else 0, ptr(sums), ptr(quant),
+                                   ptr(lineages)), "epipf_smooth")
+        mean = sums / float(self.N)
+        mean[self._last_status[:n] != _lib.STATUS_OK] = np.nan
+        return smoothing.Smoothed(mean, None if quant is None else quant.astype(np.int64), lineages, sums, None)
+
+    def smooth_history(self, hidden, ancestry, lineage, kind, q, bins):
+        """epipf_smooth_history on int32 host arrays hidden [n, T, N, C], ancestry [n, T, N] (this engine's model and N
+        are ignored): (sums [n, T, C] int64, quantiles [n, Q, T, C] int32 or None, lineages [n, T] int32)."""
+        hidden = np.ascontiguousarray(hidden, dtype=np.int32)
+        ancestry = np.ascontiguousarray(ancestry, dtype=np.int32)
+        n, T, N, C = hidden.shape
+        nq = 0 if q is None else q.size
+        sums = np.zeros((n, T, C), dtype=np.int64)
+        lineages = np.zeros((n, T), dtype=np.int32)
+        quant = np.zeros((n, nq, T, C), dtype=np.int32) if nq else None
+        check(self._L.epipf_smooth_history(self._h, n, T, N, C, ptr(hidden), ptr(ancestry), int(lineage), int(kind),
+                                           ptr(q), nq, int(bins) if nq else 0, ptr(sums), ptr(quant), ptr(lineages)),
+              "epipf_smooth_history")
+        return sums, quant, lineages
 
     def resample(self, w, u):
         w = np.ascontiguousarray(np.asarray(w, dtype=np.float64))
