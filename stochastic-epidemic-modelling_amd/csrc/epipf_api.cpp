@@ -20,6 +20,7 @@
 
 #include "../../include/epipf.h"
 #include "abc_device.hpp"
+#include "epipf_if2.hpp"
 #include "epipf_internal.hpp"
 #include "epipf_smooth.hpp"
 
@@ -545,6 +546,28 @@ int epipf_set_population(epipf_ctx* c, const double* n_population, const double*
     return EPIPF_OK;
 }
 
+// What a chain's filter needs besides theta: the observation parameter with its binary128 log splits, the weight's tie
+// tolerance, the Philox key and filter index, and the context's SSA switches (epipf_run, epipf_if2).
+static void set_chain_stream(epipf_ctx* c, ChainParam& q, double probs, uint64_t key, uint32_t f) {
+    q.probs = probs;
+    if (!(probs == c->split_p) && !(std::isnan(probs) && std::isnan(c->split_p))) {   // binary128: ~2 us
+        log_p_split(probs, &c->split[0], &c->split[1], &c->split[2], &c->split[3]);
+        c->split_p = probs;
+    }
+    q.logp = c->split[0]; q.logp_lo = c->split[1]; q.log1mp = c->split[2]; q.log1mp_lo = c->split[3];
+    // particle_weight's tie tolerance: 8x a bound on its plain column logs' error, ~8 roundings of at most half
+    // an ulp of the sum of their terms' magnitudes, 2 log n! + n (|log p| + |log1p(-p)|) at n = the population
+    const double nmax = (double)std::max(c->lf_max, 0);
+    q.tie_tol = (2.0 * std::lgamma(nmax + 1.0) * 1.01 + nmax * (std::fabs(q.logp) + std::fabs(q.log1mp)) + 1.0) *
+                0x1.0p-46 * c->tie_scale;
+    q.k0 = (uint32_t)key;
+    q.k1 = (uint32_t)(key >> 32);
+    q.f = f;
+    q.flags = (c->fast_ssa ? kChainFastSsa : 0u) | (c->seq_decide ? kChainSeqDecide : 0u);
+    q.clock_slack = c->clock_slack;
+    q.band_slack = c->band_slack;
+}
+
 static int run_impl(epipf_ctx* c, int n_chains, const double* theta, int d, int obs_model, const double* probs,
                     const uint64_t* keys, const uint32_t* filter_index, const int32_t* active, int resample_mode,
                     const int32_t* chosen, double* log_zetas_out, int32_t* status_out, int32_t* traj_out) {
@@ -570,23 +593,7 @@ static int run_impl(epipf_ctx* c, int n_chains, const double* theta, int d, int 
                 return fail(EPIPF_EINVAL, "theta[%d][%d]=%g: parameters must be finite and >= 0 (pmcmc.py:333)", ch, i, v);
             set_theta(q, w, i, v);
         }
-        q.probs = probs[ch];
-        if (!(probs[ch] == c->split_p) && !(std::isnan(probs[ch]) && std::isnan(c->split_p))) {   // binary128: ~2 us
-            log_p_split(probs[ch], &c->split[0], &c->split[1], &c->split[2], &c->split[3]);
-            c->split_p = probs[ch];
-        }
-        q.logp = c->split[0]; q.logp_lo = c->split[1]; q.log1mp = c->split[2]; q.log1mp_lo = c->split[3];
-        // particle_weight's tie tolerance: 8x a bound on its plain column logs' error, ~8 roundings of at most half
-        // an ulp of the sum of their terms' magnitudes, 2 log n! + n (|log p| + |log1p(-p)|) at n = the population
-        const double nmax = (double)std::max(c->lf_max, 0);
-        q.tie_tol = (2.0 * std::lgamma(nmax + 1.0) * 1.01 + nmax * (std::fabs(q.logp) + std::fabs(q.log1mp)) + 1.0) *
-                    0x1.0p-46 * c->tie_scale;
-        q.k0 = (uint32_t)keys[ch];
-        q.k1 = (uint32_t)(keys[ch] >> 32);
-        q.f = filter_index[ch];
-        q.flags = (c->fast_ssa ? kChainFastSsa : 0u) | (c->seq_decide ? kChainSeqDecide : 0u);
-        q.clock_slack = c->clock_slack;
-        q.band_slack = c->band_slack;
+        set_chain_stream(c, q, probs[ch], keys[ch], filter_index[ch]);
         for (int g = kMaxLaneG; w && g < kMaxG; ++g) {
             const int h = g - kMaxLaneG;
             w->npop_hi[h] = c->npop[g]; w->mu_hi[h] = c->mu[g]; w->emu_hi[h] = c->emu[g]; w->kmax_hi[h] = c->kmax[g];
@@ -1132,6 +1139,117 @@ int epipf_smooth_history(epipf_ctx* c, int n, int T, int N, int C, const int32_t
     for (size_t i = 0; i < (size_t)n * T * N; ++i)
         if (ancestry[i] < 0 || ancestry[i] >= N) return fail(EPIPF_EINVAL, "ancestors must lie in [0, N)");
     return smooth_run(c, n, T, N, C, hidden, ancestry, lineage, kind, q, n_q, bins, sums_out, quant_out, lineages_out);
+}
+
+// Iterated filtering: M passes of the filter with theta per particle, all enqueued at once.
+int epipf_if2(epipf_ctx* c, int n_searches, int iterations, double* swarm_inout, int d, const double* half_widths,
+              int obs_model, const double* probs, const uint64_t* keys, const uint32_t* filter_index0,
+              double* log_zetas_out, double* mean_out, int32_t* iterations_done_out, int32_t* status_out) {
+    if (!c || !swarm_inout || !half_widths || !probs || !keys || !filter_index0 || !mean_out || !iterations_done_out ||
+        !status_out)
+        return fail(EPIPF_EINVAL, "NULL argument");
+    if (c->model != EPIPF_SIR && c->model != EPIPF_SEIR)
+        return fail(EPIPF_EINVAL, "iterated filtering covers the SIR and SEIR models; the subgroup models are out of its scope");
+    if (!c->have_Y) return fail(EPIPF_ESTATE, "epipf_set_observations was not called");
+    if (!c->have_pop) return fail(EPIPF_ESTATE, "epipf_set_population was not called");
+    const int S = n_searches, M = iterations, N = c->N, T = c->T;
+    if (d != theta_dim(c->model, c->G)) return fail(EPIPF_EINVAL, "theta has %d entries per particle, model needs %d", d, theta_dim(c->model, c->G));
+    if (S < 1 || S > c->max_chains) return fail(EPIPF_EINVAL, "n_searches=%d outside [1, max_chains=%d]", S, c->max_chains);
+    if (M < 1) return fail(EPIPF_EINVAL, "iterations=%d must be >= 1", M);
+    if (obs_model != EPIPF_OBS_BINOMIAL && obs_model != EPIPF_OBS_NORMAL) return fail(EPIPF_EINVAL, "bad obs_model %d", obs_model);
+    for (size_t i = 0; i < (size_t)M * d; ++i)
+        if (!(half_widths[i] >= 0.0 && half_widths[i] < INFINITY))
+            return fail(EPIPF_EINVAL, "half_widths[%zu][%zu]=%g: half-widths must be finite and >= 0", i / d, i % d, half_widths[i]);
+    for (size_t i = 0; i < (size_t)S * N * d; ++i)
+        if (!(swarm_inout[i] >= 0.0 && swarm_inout[i] < INFINITY))
+            return fail(EPIPF_EINVAL, "swarm[%zu][%zu][%zu]=%g: parameters must be finite and >= 0", i / ((size_t)N * d),
+                        i / d % N, i % d, swarm_inout[i]);
+    for (int s = 0; s < S; ++s) {
+        ChainParam& q = c->h_cp[s];
+        memset(&q, 0, sizeof q);                         // theta is the particles' own (the swarm)
+        set_chain_stream(c, q, probs[s], keys[s], filter_index0[s]);
+        q.chosen = -1;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    // scratch: swarm [2][max_chains][d][N] | start [max_chains][d][N] | log_zeta [M][max_chains][T] | mean [S][M][d] | done [S]
+    const size_t comp = (size_t)d * N, mc = (size_t)c->max_chains;
+    const size_t b_swarm = align256(sizeof(double) * 2 * mc * comp), b_start = align256(sizeof(double) * mc * comp);
+    const size_t b_lz = align256(sizeof(double) * (size_t)M * mc * T), b_mean = align256(sizeof(double) * (size_t)S * M * d);
+    const size_t b_done = align256(sizeof(int32_t) * (size_t)S);
+    if (ensure_scratch(c, b_swarm + b_start + b_lz + b_mean + b_done)) return EPIPF_ENOMEM;
+    char* base = (char*)c->scratch;
+    double* d_swarm = (double*)base;
+    double* d_start = (double*)(base + b_swarm);
+    double* d_lz = (double*)(base + b_swarm + b_start);
+    double* d_mean = (double*)(base + b_swarm + b_start + b_lz);
+    int32_t* d_done = (int32_t*)(base + b_swarm + b_start + b_lz + b_mean);
+    std::vector<double> soa((size_t)S * comp);            // [S][N][d] -> [S][d][N]
+    for (int s = 0; s < S; ++s)
+        for (int j = 0; j < N; ++j)
+            for (int k = 0; k < d; ++k) soa[((size_t)s * d + k) * N + j] = swarm_inout[((size_t)s * N + j) * d + k];
+    HIP_TRY(hipMemcpyAsync(c->cp, c->h_cp, sizeof(ChainParam) * S, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_start, soa.data(), sizeof(double) * soa.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(d_lz, 0xFF, b_lz + b_mean, c->stream));     // rows never written read as NaN
+    HIP_TRY(hipMemsetAsync(d_done, 0, b_done, c->stream));
+
+    If2Args a{};
+    StepArgs& s = a.s;
+    s.N = N; s.T = T; s.max_chains = c->max_chains; s.wg = 64; s.B = c->B; s.lanes = 1; s.lane_events = 1;
+    s.resample_mode = EPIPF_RESAMPLE_MULTINOMIAL; s.lf_max = c->lf_max;
+    s.hist_stride = c->hist_stride; s.anc_stride = c->anc_stride; s.wstride = c->wstride; s.bstride = c->bstride;
+    s.seg = prefix_segment(s.B);
+    s.nseg = (s.B + s.seg - 1) / s.seg;
+    s.cert_k = cert_k(N, s.B, s.seg, 64);
+    s.Y = c->Y; s.lf = c->lf; s.logtab = c->logtab; s.cp = c->cp; s.hidden = c->hidden; s.ancestry = c->ancestry;
+    s.wraw = c->wraw; s.wloc = c->wloc; s.bsum = c->bsum; s.log_zeta = d_lz; s.status = c->status; s.counters = c->counters;
+    s.xcd_map = c->xcd_map;
+    for (int g = 0; g < kMaxLaneG; ++g) { s.npop[g] = c->npop[g]; s.mu[g] = c->mu[g]; s.emu[g] = c->emu[g]; s.kmax[g] = c->kmax[g]; }
+    a.d = d; a.M = M; a.swarm = d_swarm; a.start = d_start; a.mean = d_mean; a.done = d_done;
+
+    FilterStreams fs{};
+    fs.n = std::min(c->n_streams, S);
+    if (!ensure_streams(c, fs.n)) return fail(EPIPF_EHIP, "auxiliary stream creation failed");
+    fs.s[0] = c->stream;
+    if (fs.n > 1) HIP_TRY(hipEventRecord(c->fork, c->stream));    // the groups' inputs are on c->stream
+    for (int g = 1; g < fs.n; ++g) {
+        fs.s[g] = c->aux[g];
+        fs.join[g] = c->join[g];
+        HIP_TRY(hipStreamWaitEvent(c->aux[g], c->fork, 0));
+    }
+    c->last_groups = fs.n;
+    hipError_t le = launch_if2(a, c->model, obs_model, S, half_widths, fs);
+    if (le != hipSuccess) return fail(EPIPF_EHIP, "kernel launch failed: %s", hipGetErrorString(le));
+    std::vector<double> lz((size_t)M * mc * T), mean((size_t)S * M * d);
+    HIP_TRY(hipMemcpyAsync(soa.data(), d_start, sizeof(double) * soa.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(lz.data(), d_lz, sizeof(double) * lz.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(mean.data(), d_mean, sizeof(double) * mean.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(iterations_done_out, d_done, sizeof(int32_t) * S, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(status_out, c->status, sizeof(int32_t) * S, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    int64_t passes = 0;
+    for (int q = 0; q < S; ++q) {
+        for (int j = 0; j < N; ++j)
+            for (int k = 0; k < d; ++k) swarm_inout[((size_t)q * N + j) * d + k] = soa[((size_t)q * d + k) * N + j];
+        const int done = std::min(std::max(iterations_done_out[q], 0), M);
+        passes += std::min(done + 1, M);
+        for (int m = 0; m < M; ++m) {                    // an iteration that did not complete reports NaN
+            for (int k = 0; k < d; ++k)
+                mean_out[((size_t)q * M + m) * d + k] = m < done ? mean[((size_t)q * M + m) * d + k] : NAN;
+            if (!log_zetas_out) continue;
+            for (int p = 0; p < T; ++p)
+                log_zetas_out[((size_t)q * M + m) * T + p] = m < done ? lz[((size_t)m * mc + q) * T + p] : NAN;
+        }
+    }
+    c->stats.particle_steps += passes * N * T;
+    c->stats.filters += passes;
+    c->stats.last_lanes = 1;
+    c->stats.last_lane_events = 1;
+    c->stats.last_fused = 0;
+    c->last_chains = S;
+    c->last_T = T;
+    c->have_run = true;
+    trim_scratch(c);
+    return EPIPF_OK;
 }
 
 int epipf_glibc_log(int64_t n, const double* x, double* out) {

@@ -1,0 +1,263 @@
+// epipf_if2.hip -- the iterated-filtering kernels for MI355X (gfx950) and their launcher.
+//
+// if2_init_kernel / if2_step_kernel are pf_init_kernel / pf_step_kernel (epipf_kernels.hpp) with theta per particle:
+// one lane per particle, one wave per block, the same grid (step_block), weights (particle_weight), scans
+// (scan_block_sums / scan_segments / block_inclusive_scan) and certified resampling search.  What differs:
+//   - the filter index is the chain's plus the iteration (cp.f + m), so the M passes of a call need no upload between;
+//   - after the ancestor is known the lane gathers the ancestor's theta, jitters it (perturb) and stores it, and
+//     runs the SSA on its own ChainParam copy with that theta (rates in VGPRs instead of SGPRs);
+//   - the SSA is the certified f32 loop (fast_propagate) with the exact loop per lane for what it hands back.  The
+//     wave-cooperative replay (coop_replay) takes one wave-uniform ChainParam, which a lane's theta is not.
+// if2_finish_kernel closes an iteration of the searches still running: the swarm becomes the next iteration's start
+// and its component means are reduced in a fixed order.
+#include "epipf_if2.hpp"
+
+#include <algorithm>
+
+#include "epipf_step.hpp"
+
+namespace epipf {
+
+// theta[c] + hw[c] (2u - 1), reflected at 0; component c draws from block c / 2 of (., j, tag, f): words (0, 1) for
+// even c, (2, 3) for odd c.  No contraction (-ffp-contract=off): the restatement's roundings.
+template <int D>
+__device__ __forceinline__ void if2_perturb(double* th, const If2Args& a, uint32_t j, uint32_t tag, const ChainParam& cp) {
+#pragma unroll
+    for (int b = 0; b < (D + 1) / 2; ++b) {
+        const Block r = philox((uint32_t)b, j, tag, cp.f, cp.k0, cp.k1);
+        {
+            const double u = u01(r.x, r.y);
+            const double t = th[2 * b] + a.hw[2 * b] * (2.0 * u - 1.0);
+            th[2 * b] = (t < 0.0) ? -t : t;
+        }
+        if (2 * b + 1 < D) {
+            const double u = u01(r.z, r.w);
+            const double t = th[2 * b + 1] + a.hw[2 * b + 1] * (2.0 * u - 1.0);
+            th[2 * b + 1] = (t < 0.0) ? -t : t;
+        }
+    }
+}
+
+template <int MODEL, int OBS>
+__global__ __launch_bounds__(64) void if2_init_kernel(If2Args a) {
+    constexpr int C = Shape<MODEL, 1>::C;
+    constexpr int D = (MODEL == kSIR) ? 2 : 3;
+    constexpr int WG = 64;
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const StepArgs& s = a.s;
+    const BlockPos bp = step_block(s);
+    const int chain = bp.chain;
+    const int j = bp.b * WG + (int)threadIdx.x;
+    ChainParam cp = s.cp[chain];
+    cp.f += (uint32_t)a.m;
+    // the first iteration starts every search; a search that degenerated in an earlier one stays as it ended
+    if (a.m == 0) {
+        if (bp.b == 0 && threadIdx.x == 0) s.status[chain] = kStatusOk;
+    } else if (s.status[chain] != 0) {
+        return;
+    }
+    double x[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) x[c] = 0.0;
+    if (j < s.N) {
+        init_particle<MODEL, 1>(s, cp, j, x);                            // pmcmc.py:156-175
+        int32_t* h = s.hidden + (size_t)chain * s.hist_stride + (size_t)j * C;
+#pragma unroll
+        for (int c = 0; c < C; ++c) h[c] = (int32_t)x[c];
+        s.ancestry[(size_t)chain * s.anc_stride + j] = 0;
+        double th[D];
+#pragma unroll
+        for (int c = 0; c < D; ++c) th[c] = a.start[((size_t)chain * D + c) * s.N + j];
+        if2_perturb<D>(th, a, (uint32_t)j, kDomainIf2, cp);              // step 0
+#pragma unroll
+        for (int c = 0; c < D; ++c) a.swarm[((size_t)chain * D + c) * s.N + j] = th[c];   // buffer 0
+    }
+    if (bp.b == 0 && threadIdx.x == 0) s.log_zeta[(size_t)chain * s.T] = 0.0;
+    if (s.T > 1) {
+        double w = 0.0;
+        if (j < s.N)
+            w = particle_weight<MODEL, 1, OBS>(x, s.Y, cp, s.cp + chain, s.lf, s.lf_max,
+                                               s.hidden + (size_t)chain * s.hist_stride + (size_t)j * C);
+        const size_t wbase = (size_t)chain * s.wstride;                  // buffer 0
+        const double loc = block_inclusive_scan<WG>(w, smem);
+        s.wraw[wbase + j] = w;
+        s.wloc[wbase + j] = loc;
+        if ((int)threadIdx.x == WG - 1) s.bsum[(size_t)chain * s.bstride + bp.b] = loc;
+    }
+}
+
+template <int MODEL, int OBS>
+__global__ __launch_bounds__(64) void if2_step_kernel(If2Args a, int p) {
+    constexpr int C = Shape<MODEL, 1>::C;
+    constexpr int K = Shape<MODEL, 1>::K;
+    constexpr int D = (MODEL == kSIR) ? 2 : 3;
+    constexpr int WG = 64;
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const StepArgs& s = a.s;
+    LogTab* tab = reinterpret_cast<LogTab*>(smem);       // the layout of pf_step_kernel (step_lds_bytes)
+    double* red = smem + 2 * kLogTabEntries;
+    double* seg_start = red + 16;
+    double* seg_end = seg_start + s.nseg;
+    const BlockPos bp = step_block(s);
+    const int chain = bp.chain;
+    const int tid = threadIdx.x;
+    const int j = bp.b * WG + tid;
+    if (s.status[chain] != 0) return;
+    ChainParam cp = s.cp[chain];
+    cp.f += (uint32_t)a.m;
+    const int prev = (p - 1) & 1, cur = p & 1;
+    const size_t wprev = ((size_t)prev * s.max_chains + chain) * s.wstride;
+    const size_t wcur = ((size_t)cur * s.max_chains + chain) * s.wstride;
+    const size_t bprev = ((size_t)prev * s.max_chains + chain) * s.bstride;
+    const size_t bcur = ((size_t)cur * s.max_chains + chain) * s.bstride;
+
+    // likelihood of the perturbed model: zetas[p] = zetas[p-1] * mean(w), in log space (pf_step_kernel)
+    const double total = (s.seg == 1) ? scan_block_sums<WG>(s.bsum + bprev, s.B, seg_start + s.B, seg_start, red)
+                                      : scan_segments(s.bsum + bprev, s.B, s.seg, s.nseg, seg_start, seg_end);
+    if (!(total > 0.0)) {                                // all weights 0 or NaN: this search ends here
+        if (bp.b == 0 && tid == 0) {
+            s.status[chain] = kStatusDegenerate;
+            s.log_zeta[(size_t)chain * s.T + p] = -__builtin_inf();
+        }
+        return;
+    }
+    if (bp.b == 0 && tid == 0)
+        s.log_zeta[(size_t)chain * s.T + p] = s.log_zeta[(size_t)chain * s.T + p - 1] + log(total / (double)s.N);
+
+    // multinomial draw and certified search, exactly the filter's
+    double U = 0.0;
+    int anc = 0;
+    bool certified = true, ambiguous = false;
+    if (j < s.N) {
+        const Block r = philox(0u, (uint32_t)j, ((uint32_t)p & 0xFFFFFFu) | kDomainResample, cp.f, cp.k0, cp.k1);
+        U = u01(r.x, r.y);
+        if (s.seg == 1)
+            anc = resample_search<WG>(U, seg_start + s.B, seg_start, s.B, total, s.wloc + wprev, s.N, s.cert_k,
+                                      certified, 0.0, ambiguous);
+        else
+            anc = resample_search_seg(U, seg_start, seg_end, s.nseg, s.seg, s.bsum + bprev, s.B, total,
+                                      s.wloc + wprev, WG, s.N, s.cert_k, certified, 0.0, ambiguous);
+    }
+    if (__any(!certified)) {   // wave-uniform: the whole wave resolves its uncertified draws exactly
+        const int e = resample_exact_wave(!certified, U, s.wraw + wprev, s.N);
+        if (!certified) {
+            anc = e;
+            atomicAdd(counter_slot(s.counters) + 1, 1ull);
+        }
+    }
+    // the ancestor's theta, jittered: this particle's rates.  The lane's own ChainParam copy differs from the chain's
+    // in theta and thetaf only.
+    double x[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) x[c] = 0.0;
+    const uint32_t ptag = ((uint32_t)p & 0xFFFFFFu) | kDomainSSA;
+    ChainParam lcp = cp;
+    bool fast_ok = true, eligible = false;
+    int nev = 0, iters = 0;
+    if (j < s.N) {
+        anc = checked_index(anc, s.N);
+        s.ancestry[(size_t)chain * s.anc_stride + (size_t)p * s.N + j] = anc;
+        double th[D];
+#pragma unroll
+        for (int c = 0; c < D; ++c) th[c] = a.swarm[(((size_t)prev * s.max_chains + chain) * D + c) * s.N + anc];
+        if2_perturb<D>(th, a, (uint32_t)j, ((uint32_t)p & 0xFFFFFFu) | kDomainIf2, cp);
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+            a.swarm[(((size_t)cur * s.max_chains + chain) * D + c) * s.N + j] = th[c];
+            lcp.theta[c] = th[c];
+            lcp.thetaf[c] = (float)th[c];
+        }
+        const int32_t* hp = s.hidden + (size_t)chain * s.hist_stride + ((size_t)(p - 1) * s.N + anc) * C;
+#pragma unroll
+        for (int c = 0; c < C; ++c) x[c] = (double)hp[c];
+        fast_ok = fast_propagate<MODEL, 1>(x, lcp, (uint32_t)j, ptag, 1.0, nev, iters, eligible);
+    }
+    // lanes the f32 loop could not run or could not certify at the step boundary: the exact loop from the untouched
+    // parent state, per lane.  Its log table goes to LDS only in waves that need it (one wave per block, so the test
+    // is block-uniform and the barrier legal).
+    if (__any(!fast_ok)) {
+        for (int i = tid; i < kLogTabEntries; i += WG) tab[i] = s.logtab[i];
+        __syncthreads();
+        if (!fast_ok) nev = exact_propagate<MODEL, 1>(x, lcp, (uint32_t)j, ptag, 1.0, tab, iters);
+    }
+    double w = 0.0;
+    if (j < s.N) {
+        int32_t* hc = s.hidden + (size_t)chain * s.hist_stride + ((size_t)p * s.N + j) * C;
+#pragma unroll
+        for (int c = 0; c < C; ++c) hc[c] = (int32_t)x[c];
+        if (p + 1 < s.T) w = particle_weight<MODEL, 1, OBS>(x, s.Y + (size_t)p * K, cp, s.cp + chain, s.lf, s.lf_max, hc);
+    }
+    if (p + 1 < s.T) {
+        const double loc = block_inclusive_scan<WG>(w, red);
+        s.wraw[wcur + j] = w;
+        s.wloc[wcur + j] = loc;
+        if (tid == WG - 1) s.bsum[bcur + bp.b] = loc;
+    }
+}
+
+// End of iteration m for the searches still running: block (c, search) copies component c of the final swarm (buffer
+// (T - 1) & 1) to the start copy and reduces its mean: each thread's strided partial sum, then the 256 partials in
+// thread order by one thread (a fixed order: the same bits on every run).
+__global__ __launch_bounds__(256) void if2_finish_kernel(If2Args a) {
+    __shared__ double part[256];
+    const StepArgs& s = a.s;
+    const int c = blockIdx.x, chain = s.chain0 + (int)blockIdx.y;
+    if (s.status[chain] != 0) return;
+    const int last = (s.T - 1) & 1;
+    const double* src = a.swarm + (((size_t)last * s.max_chains + chain) * a.d + c) * s.N;
+    double* dst = a.start + ((size_t)chain * a.d + c) * s.N;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < s.N; i += 256) {
+        const double v = src[i];
+        dst[i] = v;
+        acc = acc + v;
+    }
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot = 0.0;
+        for (int i = 0; i < 256; ++i) tot = tot + part[i];
+        a.mean[((size_t)chain * a.M + a.m) * a.d + c] = tot / (double)s.N;
+        if (c == 0) a.done[chain] = a.m + 1;
+    }
+}
+
+template <int MODEL, int OBS>
+static hipError_t launch_if2_t(const If2Args& a, int n_searches, const double* half_widths, const FilterStreams& fs) {
+    const StepArgs& s0 = a.s;
+    const size_t lds = step_lds_bytes(s0.B, 64);
+    const int S = std::max(1, std::min(fs.n, n_searches));
+    for (int g = 0; g < S; ++g) {
+        If2Args ag = a;
+        ag.s.chain0 = (int)((long)n_searches * g / S);
+        const int n_g = (int)((long)n_searches * (g + 1) / S) - ag.s.chain0;
+        const hipStream_t st = fs.s[g];
+        ag.s.xcd_map = s0.xcd_map && (long)s0.B * n_g * 64 < (1L << 31);
+        const dim3 grid = ag.s.xcd_map ? dim3(s0.B * n_g) : dim3(s0.B, n_g), block(64);
+        for (int m = 0; m < a.M; ++m) {
+            ag.m = m;
+            for (int c = 0; c < a.d; ++c) ag.hw[c] = half_widths[(size_t)m * a.d + c];
+            ag.s.log_zeta = s0.log_zeta + (size_t)m * s0.max_chains * s0.T;
+            hipLaunchKernelGGL((if2_init_kernel<MODEL, OBS>), grid, block, lds, st, ag);
+            for (int p = 1; p < s0.T; ++p) hipLaunchKernelGGL((if2_step_kernel<MODEL, OBS>), grid, block, lds, st, ag, p);
+            hipLaunchKernelGGL(if2_finish_kernel, dim3(a.d, n_g), dim3(256), 0, st, ag);
+        }
+        if (g > 0) (void)hipEventRecord(fs.join[g], st);
+    }
+    for (int g = 1; g < S; ++g) (void)hipStreamWaitEvent(fs.s[0], fs.join[g], 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_if2(const If2Args& a, int model, int obs, int n_searches, const double* half_widths,
+                      const FilterStreams& fs) {
+    if (a.s.wg != 64 || a.s.lanes != 1 || a.M < 1) return hipErrorInvalidValue;
+    if (model == kSIR && a.d == 2)
+        return obs == kBinomial ? launch_if2_t<kSIR, kBinomial>(a, n_searches, half_widths, fs)
+                                : launch_if2_t<kSIR, kNormal>(a, n_searches, half_widths, fs);
+    if (model == kSEIR && a.d == 3)
+        return obs == kBinomial ? launch_if2_t<kSEIR, kBinomial>(a, n_searches, half_widths, fs)
+                                : launch_if2_t<kSEIR, kNormal>(a, n_searches, half_widths, fs);
+    return hipErrorInvalidValue;
+}
+
+}  // namespace epipf

@@ -164,6 +164,34 @@ class Engine:
         _PARTICLE_STEPS[0] += (n if act is None else int(np.count_nonzero(act))) * self.N * self.T
         return (lz, st) if chosen is None else (lz, st, tr)
 
+    def if2(self, swarm, half_widths, probs, keys, filter_index0, observations=False):
+        """epipf_if2: iterated filtering from the swarms [S, N, d] with the half-width table [M, d], search s at filter
+        indices filter_index0[s] + m.  Returns (swarm [S, N, d], mean [S, M, d], log_zetas [S, M, T],
+        iterations_done [S], status [S]); history() afterwards holds each search's last executed pass."""
+        swarm = np.array(swarm, dtype=np.float64, order="C")          # a copy: the library writes the result into it
+        hw = np.ascontiguousarray(np.asarray(half_widths, dtype=np.float64))
+        if swarm.ndim != 3 or swarm.shape[1] != self.N:
+            raise ValueError(f"swarm must be [searches, {self.N}, d]")
+        S, _, d = swarm.shape
+        if hw.ndim != 2 or hw.shape[1] != d:
+            raise ValueError(f"half_widths must be [iterations, {d}]")
+        M = hw.shape[0]
+        probs = np.ascontiguousarray(np.broadcast_to(np.asarray(probs, dtype=np.float64), (S,)))
+        keys = np.ascontiguousarray(np.broadcast_to(np.asarray(keys, dtype=np.uint64), (S,)))
+        f0 = np.ascontiguousarray((np.broadcast_to(np.asarray(filter_index0, dtype=np.uint64), (S,))
+                                   & np.uint64(0xFFFFFFFF)).astype(np.uint32))
+        lz = np.empty((S, M, self.T), dtype=np.float64)
+        mean = np.empty((S, M, d), dtype=np.float64)
+        done = np.zeros(S, dtype=np.int32)
+        st = np.empty(S, dtype=np.int32)
+        obs = _lib.OBS_NORMAL if observations else _lib.OBS_BINOMIAL
+        check(self._L.epipf_if2(self._h, S, M, ptr(swarm), d, ptr(hw), obs, ptr(probs), ptr(keys), ptr(f0), ptr(lz),
+                                ptr(mean), ptr(done), ptr(st)), "epipf_if2")
+        self._last_n = S
+        self._last_status = st.copy()
+        _PARTICLE_STEPS[0] += int(np.minimum(done + 1, M).sum()) * self.N * self.T
+        return swarm, mean, lz, done, st
+
     def history(self, n_chains=None):
         """(hidden [n, T, N, C] int32, ancestry [n, T, N] int32) of the last run."""
         n = self._last_n if n_chains is None else int(n_chains)
