@@ -91,8 +91,9 @@ typedef struct {
     double abc_ms;               /* HIP-event time of the ABC trial kernels (profiling on) */
     int64_t abc_launches;        /* ABC trial kernel launches */
     int64_t abc_trials;          /* ABC trials simulated (accepted or not) */
-    int64_t ssa_exact_lanes;     /* filter particle-steps simulated on the exact f64 SSA loop (profiling counters) */
-    int64_t ssa_exact_waves;     /* filter wave-steps with at least one such particle-step */
+    int64_t ssa_exact_lanes;     /* particle-steps of a filter or of iterated filtering (epipf_if2) simulated on the exact
+                                    f64 SSA loop (profiling counters) */
+    int64_t ssa_exact_waves;     /* wave-steps of either with at least one such particle-step */
     double step_kernel_ms;       /* summed span of each chain group's back-to-back step kernels, HIP events on the
                                     group's own stream (profiling on) */
     int64_t step_kernel_launches;/* their number: one step of all chains (step_ms) is one launch per chain group on
@@ -285,7 +286,10 @@ int epipf_abc_smc_weights(epipf_ctx* ctx, const double* theta, int n, const doub
  * iteration found it, its mean_out / log_zetas_out rows from that iteration on are NaN, and the other searches are not
  * affected.  T == 1 is valid (only the step-0 jitter runs).  Every launch of the call is enqueued without host
  * synchronisation.  Afterwards epipf_copy_history / epipf_path_sample / epipf_smooth see the last executed pass of each
- * search.  EPIPF_EINVAL on a subgroup context: those models are out of scope. */
+ * search.  EPIPF_EINVAL on a subgroup context: those models are out of scope.
+ * epipf_get_stats afterwards: resample_fallbacks of this call, and at EPIPF_PROFILE_COUNTERS its events,
+ * lane_iterations, wave_lane_slots, ssa_exact_lanes and ssa_exact_waves (a failed iteration's steps before the dying one
+ * included).  The device counters are left cleared: the next epipf_run reports its own counts only. */
 int epipf_if2(epipf_ctx* ctx, int n_searches, int iterations, double* swarm_inout, int d, const double* half_widths,
               int obs_model, const double* probs, const uint64_t* keys, const uint32_t* filter_index0,
               double* log_zetas_out, double* mean_out, int32_t* iterations_done_out, int32_t* status_out);

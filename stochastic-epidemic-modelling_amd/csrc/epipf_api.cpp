@@ -1191,11 +1191,16 @@ int epipf_if2(epipf_ctx* c, int n_searches, int iterations, double* swarm_inout,
     HIP_TRY(hipMemcpyAsync(d_start, soa.data(), sizeof(double) * soa.size(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(d_lz, 0xFF, b_lz + b_mean, c->stream));     // rows never written read as NaN
     HIP_TRY(hipMemsetAsync(d_done, 0, b_done, c->stream));
+    // the device counters of this call alone: cleared here and again once harvested, so that neither an earlier run's
+    // counts are reported as this call's nor this call's as the next epipf_run's
+    const size_t b_counters = sizeof(unsigned long long) * (size_t)kCounterSlots * kCounterStride;
+    HIP_TRY(hipMemsetAsync(c->counters, 0, b_counters, c->stream));
 
     If2Args a{};
     StepArgs& s = a.s;
     s.N = N; s.T = T; s.max_chains = c->max_chains; s.wg = 64; s.B = c->B; s.lanes = 1; s.lane_events = 1;
     s.resample_mode = EPIPF_RESAMPLE_MULTINOMIAL; s.lf_max = c->lf_max;
+    s.count_events = c->profiling >= EPIPF_PROFILE_COUNTERS ? 1 : 0;
     s.hist_stride = c->hist_stride; s.anc_stride = c->anc_stride; s.wstride = c->wstride; s.bstride = c->bstride;
     s.seg = prefix_segment(s.B);
     s.nseg = (s.B + s.seg - 1) / s.seg;
@@ -1225,7 +1230,20 @@ int epipf_if2(epipf_ctx* c, int n_searches, int iterations, double* swarm_inout,
     HIP_TRY(hipMemcpyAsync(mean.data(), d_mean, sizeof(double) * mean.size(), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(iterations_done_out, d_done, sizeof(int32_t) * S, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(status_out, c->status, sizeof(int32_t) * S, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_counters, c->counters, b_counters, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemsetAsync(c->counters, 0, b_counters, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    unsigned long long tot[kNumCounters] = {};
+    for (int sl = 0; sl < kCounterSlots; ++sl)
+        for (int k = 0; k < kNumCounters; ++k) tot[k] += c->h_counters[(size_t)sl * kCounterStride + k];
+    c->stats.resample_fallbacks = (int64_t)tot[1];       // counted at every profiling level, as in epipf_run
+    if (s.count_events) {
+        c->stats.events = (int64_t)tot[0];
+        c->stats.lane_iterations = (int64_t)tot[2];
+        c->stats.wave_lane_slots = (int64_t)tot[3];
+        c->stats.ssa_exact_lanes = (int64_t)tot[4];
+        c->stats.ssa_exact_waves = (int64_t)tot[5];
+    }
     int64_t passes = 0;
     for (int q = 0; q < S; ++q) {
         for (int j = 0; j < N; ++j)

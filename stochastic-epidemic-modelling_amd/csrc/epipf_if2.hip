@@ -7,7 +7,9 @@
 //   - after the ancestor is known the lane gathers the ancestor's theta, jitters it (perturb) and stores it, and
 //     runs the SSA on its own ChainParam copy with that theta (rates in VGPRs instead of SGPRs);
 //   - the SSA is the certified f32 loop (fast_propagate) with the exact loop per lane for what it hands back.  The
-//     wave-cooperative replay (coop_replay) takes one wave-uniform ChainParam, which a lane's theta is not.
+//     wave-cooperative replay (coop_replay) takes one wave-uniform ChainParam, which a lane's theta is not;
+//   - with count_events the step kernel adds to pf_step_kernel's counter slots (events, lane and wave iterations, exact
+//     particle-steps and their waves), which epipf_if2 harvests and clears.
 // if2_finish_kernel closes an iteration of the searches still running: the swarm becomes the next iteration's start
 // and its component means are reduced in a fixed order.
 #include "epipf_if2.hpp"
@@ -179,6 +181,24 @@ __global__ __launch_bounds__(64) void if2_step_kernel(If2Args a, int p) {
         for (int i = tid; i < kLogTabEntries; i += WG) tab[i] = s.logtab[i];
         __syncthreads();
         if (!fast_ok) nev = exact_propagate<MODEL, 1>(x, lcp, (uint32_t)j, ptag, 1.0, tab, iters);
+    }
+    if (s.count_events) {  // pf_step_kernel's counters, before the weights so that nev and iters die here
+        unsigned long long e = (unsigned long long)nev, li = (unsigned long long)iters;
+        int wmax = iters;
+        for (int o = 32; o > 0; o >>= 1) {
+            e += __shfl_xor(e, o, 64);
+            li += __shfl_xor(li, o, 64);
+            wmax = max(wmax, __shfl_xor(wmax, o, 64));
+        }
+        const unsigned long long ex = __ballot(!fast_ok);             // lanes past N hold fast_ok = true
+        if (tid == 0) {
+            unsigned long long* slot = counter_slot(s.counters);
+            atomicAdd(slot, e);
+            atomicAdd(slot + 2, li);
+            atomicAdd(slot + 3, 64ull * (unsigned long long)wmax);
+            atomicAdd(slot + 4, (unsigned long long)__popcll(ex));    // particle-steps on the exact SSA loop
+            atomicAdd(slot + 5, ex ? 1ull : 0ull);                    // waves with at least one
+        }
     }
     double w = 0.0;
     if (j < s.N) {

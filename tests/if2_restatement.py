@@ -51,7 +51,8 @@ def weights(model, x, yrow, observations, probs):
 
 def one_pass(Y, model, theta, hw, observations, probs, npop, mu, key, f):
     """One iteration at filter index f from the swarm theta [N, d].  Returns dict(status, theta [N, d] (the swarm
-    after the last step), hidden [T, N, C], ancestry [T, N], log_zetas [T], reflections)."""
+    after the last step), hidden [T, N, C], ancestry [T, N], log_zetas [T], reflections, events (accepted SSA events of
+    the steps that ran))."""
     Y = np.asarray(Y, dtype=np.float64)
     T = Y.shape[0]
     theta = np.asarray(theta, dtype=np.float64)
@@ -63,7 +64,7 @@ def one_pass(Y, model, theta, hw, observations, probs, npop, mu, key, f):
     anc = np.zeros((T, N), dtype=np.int32)
     lz = np.zeros(T)
     hidden[0] = first["hidden"][0]
-    reflections = 0
+    reflections, events = 0, 0
 
     def jitter(th, p):
         nonlocal reflections
@@ -92,36 +93,62 @@ def one_pass(Y, model, theta, hw, observations, probs, npop, mu, key, f):
         for j in range(N):
             rows = np.zeros((j + 1, C), dtype=np.int32)  # rows before j hold no infection: they draw nothing
             rows[j] = hidden[p - 1, a[j]]
-            hidden[p, j] = oracle.simulate(model, rows, tuple(th[j]), 1.0, key, f, p)[0][j]
-    return dict(status=status, theta=th, hidden=hidden, ancestry=anc, log_zetas=lz, reflections=reflections)
+            out, nev = oracle.simulate(model, rows, tuple(th[j]), 1.0, key, f, p)
+            hidden[p, j] = out[j]
+            events += nev
+    return dict(status=status, theta=th, hidden=hidden, ancestry=anc, log_zetas=lz, reflections=reflections,
+                events=events)
+
+
+def device_mean(swarm):
+    """Component means of swarm [N, d] in if2_finish_kernel's order: partial[t] is the left-to-right sum of
+    swarm[t::256, c] (0.0 for an empty stride), the total the left-to-right sum of the 256 partials, over float(N)."""
+    swarm = np.asarray(swarm, dtype=np.float64)
+    N, d = swarm.shape
+    mean = np.empty(d)
+    for c in range(d):
+        tot = 0.0
+        for t in range(256):
+            acc = 0.0
+            for v in swarm[t::256, c]:
+                acc = acc + float(v)
+            tot = tot + acc
+        mean[c] = tot / float(N)
+    return mean
 
 
 def run(Y, model, swarm, hw, observations, probs, npop, mu, key, f0):
     """M = len(hw) iterations from the swarm [N, d] at filter indices f0, f0 + 1, ...  Returns dict(swarm, mean [M, d],
     loglik [M], log_zetas [M, T], status, iterations_done, hidden, ancestry, last_log_zetas (of the last executed
-    iteration), reflections)."""
+    iteration), reflections, events [M] (accepted SSA events over particles and steps of each executed iteration, a
+    failed one's steps before the dying one included), swarms [iterations_done, N, d] (each completed iteration's))."""
     swarm = np.array(swarm, dtype=np.float64)
     hw = np.asarray(hw, dtype=np.float64)
     M, T = hw.shape[0], np.asarray(Y).shape[0]
     mean = np.full((M, swarm.shape[1]), np.nan)
     loglik = np.full(M, np.nan)
     lzs = np.full((M, T), np.nan)
+    events = np.zeros(M, dtype=np.int64)
+    swarms = []
     status, done, reflections = 0, 0, 0
     last = None
     for m in range(M):
         last = one_pass(Y, model, swarm, hw[m], observations, probs, npop, mu, key, (f0 + m) & 0xFFFFFFFF)
         reflections += last["reflections"]
+        events[m] = last["events"]
         if last["status"]:
             status = last["status"]
             break
         swarm = last["theta"]
+        swarms.append(swarm)
         mean[m] = swarm.mean(axis=0)
         loglik[m] = last["log_zetas"][-1]
         lzs[m] = last["log_zetas"]
         done = m + 1
     return dict(swarm=swarm, mean=mean, loglik=loglik, log_zetas=lzs, status=status, iterations_done=done,
                 hidden=last["hidden"], ancestry=last["ancestry"], last_log_zetas=last["log_zetas"],
-                reflections=reflections)
+                reflections=reflections, events=events,
+                swarms=np.array(swarms).reshape(done, swarm.shape[0], swarm.shape[1]))
 
 
 def cooling_table(rw, cooling, iterations, first=0):

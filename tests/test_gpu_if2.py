@@ -64,6 +64,7 @@ def check_anchor(eng, model, theta, observations, T):
         np.testing.assert_array_equal(ianc, anc)
         lz_close(ilz[0, 0], lz[0])
         mean_close(mean[0, 0], swarm[0])
+        np.testing.assert_array_equal(mean[0, 0], rs.device_mean(swarm[0]))
     else:                                                # both die at the same step; the rows before it agree
         dead = int(np.argmax(np.isneginf(lz[0])))
         assert done[0] == 0 and np.isnan(mean).all() and np.isnan(ilz).all()
@@ -104,22 +105,29 @@ def restated(fx):
     return out
 
 
-def check_against(eng, r, swarm0, hw, probs, key, f):
-    swarm, mean, lz, done, st = eng.if2(swarm0[None], hw, probs, key, f)
-    hid, anc = eng.history(1)
-    assert st[0] == r["status"] and done[0] == r["iterations_done"]
-    np.testing.assert_array_equal(swarm[0], r["swarm"])
+def check_search(r, swarm, mean, lz, done, st, hid, anc):
+    """One search's results (the arrays of Engine.if2 and Engine.history at its index) against the restatement r."""
+    assert st == r["status"] and done == r["iterations_done"]
+    np.testing.assert_array_equal(swarm, r["swarm"])
     # a pass that died at a step leaves the rows from that step on unwritten, as epipf_run does
-    rows = r["hidden"].shape[0] if st[0] == 0 else int(np.argmax(np.isneginf(r["last_log_zetas"])))
-    np.testing.assert_array_equal(hid[0, :rows], r["hidden"][:rows])
-    np.testing.assert_array_equal(anc[0, :rows], r["ancestry"][:rows])
-    for m in range(done[0]):
-        lz_close(lz[0, m], r["log_zetas"][m])
-    assert np.isnan(lz[0, done[0]:]).all() and np.isnan(mean[0, done[0]:]).all()
-    if done[0]:
-        mean_close(mean[0, done[0] - 1], swarm[0])
+    rows = r["hidden"].shape[0] if st == 0 else int(np.argmax(np.isneginf(r["last_log_zetas"])))
+    np.testing.assert_array_equal(hid[:rows], r["hidden"][:rows])
+    np.testing.assert_array_equal(anc[:rows], r["ancestry"][:rows])
+    for m in range(done):
+        lz_close(lz[m], r["log_zetas"][m])
+    assert np.isnan(lz[done:]).all() and np.isnan(mean[done:]).all()
+    if done:
+        mean_close(mean[done - 1], swarm)
         # the restatement's means are np.mean of each iteration's swarm, and the swarms are equal
-        np.testing.assert_allclose(mean[0, :done[0]], r["mean"][:done[0]], rtol=2.0 * swarm.shape[1] * 2.0 ** -53, atol=0.0)
+        np.testing.assert_allclose(mean[:done], r["mean"][:done], rtol=2.0 * swarm.shape[0] * 2.0 ** -53, atol=0.0)
+    for m in range(done):                                # and in the finish kernel's summation order, bit for bit
+        np.testing.assert_array_equal(mean[m], rs.device_mean(r["swarms"][m]))
+
+
+def check_against(eng, r, swarm0, hw, probs, key, f, observations=False):
+    swarm, mean, lz, done, st = eng.if2(swarm0[None], hw, probs, key, f, observations=observations)
+    hid, anc = eng.history(1)
+    check_search(r, swarm[0], mean[0], lz[0], int(done[0]), int(st[0]), hid[0], anc[0])
     return swarm, mean
 
 
@@ -287,6 +295,7 @@ def test_the_search_finds_the_peak(fx):
     assert res.status.tolist() == [0] and res.iterations_done.tolist() == [s["M"]] and res.best == 0
     np.testing.assert_array_equal(res.swarm[0], r["swarm"])
     mean_close(res.theta[0], res.swarm[0])
+    np.testing.assert_array_equal(res.theta[0], rs.device_mean(r["swarm"]))
     np.testing.assert_allclose(res.theta[0], r["mean"][-1], rtol=2.0 * s["N"] * 2.0 ** -53, atol=0.0)
     lz_close(res.loglik[0], r["loglik"])
     start = rs.score(fx["sir"], "sir", s["start"], False, fx["probs"], fx["npop"], fx["mu"])

@@ -1,11 +1,13 @@
 """The numpy restatement of iterated filtering (tests/if2_restatement.py) against the CPU oracle: with no
 jitter it is the oracle's particle filter bit for bit, and on the small SIR fixture it finds the likelihood's peak,
-degenerates from a hopeless start, and reflects at 0.  No GPU."""
+degenerates from a hopeless start, and reflects at 0; and what each input of the device's path tests (tests/if2_cases.py,
+tests/test_gpu_if2_paths.py) contains.  No GPU."""
 import os
 
 import numpy as np
 import pytest
 
+import if2_cases as ic
 import if2_restatement as rs
 import oracle
 from conftest import GOLDEN
@@ -86,3 +88,91 @@ def test_reflection_keeps_theta_non_negative(fixture):
     u = rs.perturb_uniforms(5, 0, 0, SETTINGS["N"], 2)
     t = 0.01 + 0.05 * (2.0 * u - 1.0)
     np.testing.assert_array_equal(rs.perturb(swarm, hw[0], 5, 0, 0), np.abs(t))
+
+
+# ------------------------------------------------------------------------- the inputs of tests/test_gpu_if2_paths.py
+@pytest.fixture(scope="module")
+def fx():
+    return ic.load_fixture()
+
+
+def completes(c, M=2):
+    r = ic.restate(c)
+    assert r["status"] == 0 and r["iterations_done"] == M and len(r["swarms"]) == M
+    assert np.isfinite(r["mean"]).all() and np.isfinite(r["log_zetas"]).all() and (r["events"] > 0).all()
+    return r
+
+
+@pytest.mark.parametrize("model,N,T", [("sir", 300, 5), ("seir", 300, 5), ("sir", 700, 3), ("sir", 70, 1), ("sir", 70, 2),
+                                       ("sir", 70, 3), ("sir", 1, 3)])
+def test_multi_block_and_short_cases_complete_with_distinct_rows(fx, model, N, T):
+    """Cases 1 and 2: every row of the final swarm differs from every other."""
+    c = ic.case(fx, model, N, T)
+    r = ic.restate(c) if T == 1 else completes(c)
+    assert r["status"] == 0 and r["iterations_done"] == 2 and ic.distinct(r["swarm"]) == N
+    if T == 1:                                           # no step: the iteration's swarm is its step-0 jitter
+        assert r["events"].tolist() == [0, 0]
+        first = rs.perturb(c["swarm0"], c["hw"][0], ic.KEY, ic.F, 0)
+        np.testing.assert_array_equal(r["swarms"][0], first)
+        np.testing.assert_array_equal(r["swarm"], rs.perturb(first, c["hw"][1], ic.KEY, ic.F + 1, 0))
+
+
+@pytest.mark.parametrize("model", ["sir", "seir"])
+@pytest.mark.parametrize("observations", [True, False])
+def test_seven_day_cases_complete(fx, model, observations):
+    """Case 3 (normal observations) and its binomial twin (case 7's input): N = 130, T = 7."""
+    r = completes(ic.case(fx, model, 130, 7, observations=observations))
+    assert ic.distinct(r["swarm"]) == 130
+
+
+@pytest.mark.parametrize("key", sorted(ic.LATE))
+def test_late_degeneracy_keys(fx, key):
+    """Case 5: the search completes `done` iterations, then dies at the given step of the next one."""
+    status, done, step = ic.LATE[key]
+    r = ic.restate(ic.late_case(fx, key))
+    assert (r["status"], r["iterations_done"], ic.dying_step(r)) == (status, done, step)
+    assert np.isfinite(r["mean"][:done]).all() and np.isnan(r["mean"][done:]).all()
+    assert np.isfinite(r["log_zetas"][:done]).all() and np.isnan(r["log_zetas"][done:]).all()
+    np.testing.assert_array_equal(r["swarm"], r["swarms"][done - 1])     # the last completed iteration's
+
+
+@pytest.mark.parametrize("npop,mu,T", [(10 ** 6, 400, 6), (2 * 10 ** 4, 40, 8)])
+@pytest.mark.parametrize("observations", [False, True])
+def test_population_cases_complete(fx, npop, mu, T, observations):
+    """Case 6: S I reaches 10^9 and more at the larger population, and every search completes."""
+    c = ic.population_case(fx, npop, mu, T, observations)
+    r = completes(c)
+    assert ic.distinct(r["swarm"]) > 1
+    if npop == 10 ** 6:
+        assert (r["hidden"][:, :, 0].astype(np.int64) * r["hidden"][:, :, 1]).max() >= 10 ** 9
+
+
+@pytest.mark.parametrize("T", [2, 7])
+@pytest.mark.parametrize("odd_beta", [0.0, 1e-30])
+def test_mixed_rate_cases_complete(fx, T, odd_beta):
+    """Case 8: beta is never jittered, so the swarm holds the two start values only; at T = 2 it keeps both."""
+    r = completes(ic.mixed_case(fx, T, odd_beta))
+    assert set(np.unique(r["swarm"][:, 0])) <= {0.8, odd_beta}
+    if T == 2:
+        assert set(np.unique(r["swarm"][:, 0])) == {0.8, odd_beta}
+
+
+@pytest.mark.parametrize("theta", [(0.0, 0.3), (0.8, 0.0), (0.0, 0.0)])
+def test_zero_rate_anchors_complete(fx, theta):
+    """Case 8's anchors: the oracle filter completes at N = 70, T = 4 with a rate of zero."""
+    o = oracle.particle_filter(fx["sir"][:4], "sir", theta, False, 0.5, 70, fx["npop"], fx["mu"], key=ic.KEY,
+                               filter_index=ic.F)
+    assert o["status"] == 0
+
+
+@pytest.mark.parametrize("N", [1, 70, 256, 257, 700])
+def test_device_mean_is_the_mean(N):
+    """The finish kernel's summation order against np.mean: 2 N 2^-53 relative, any order of non-negative terms."""
+    swarm = np.random.default_rng(N).uniform(0.0, 2.0, (N, 3))
+    got, want = rs.device_mean(swarm), swarm.mean(axis=0)
+    assert (np.abs(got - want) <= 2.0 * N * 2.0 ** -53 * np.abs(want)).all()
+    if N <= 256:                                         # one value per stride: the plain left-to-right sum
+        tot = np.zeros(3)
+        for row in swarm:
+            tot = tot + row
+        np.testing.assert_array_equal(got, tot / float(N))
