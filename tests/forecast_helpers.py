@@ -1,7 +1,11 @@
-"""Shared by tests/test_forecast_host.py and tests/test_gpu_forecast.py: daily rows of an event path by the forecast's
-row rule and by the reference's traj_inf rule (tests/pred_tmps.py:55-64, restated), and oracle forecasts."""
+"""Shared by tests/test_forecast_host.py, tests/test_gpu_forecast.py and tests/test_gpu_forecast_draws.py: daily rows of
+an event path by the forecast's row rule and by the reference's traj_inf rule (tests/pred_tmps.py:55-64, restated),
+oracle forecasts, and the oracle's forecasts of tests/forecast_cases.py, computed once."""
+import functools
+
 import numpy as np
 
+import forecast_cases
 import oracle
 
 
@@ -47,3 +51,53 @@ def oracle_forecast(model, thetas, states, H, R, key, filter_index, step=0):
             rows[d, r] = bin_rows(states[d], t[r, :n[r]], x[r, :n[r]], H)
             assert np.array_equal(rows[d, r, -1], fin[r])      # no event at exactly t = H in these cases
     return rows, nev
+
+
+def _one_thread(fn):
+    """A forecast's oracle calls hold at most a few hundred paths each: the oracle's thread pool only costs there."""
+    @functools.wraps(fn)
+    def run(*args):
+        n = oracle.num_threads()
+        oracle.set_num_threads(1)
+        try:
+            return fn(*args)
+        finally:
+            oracle.set_num_threads(n)
+    return run
+
+
+@functools.lru_cache(maxsize=None)
+@_one_thread
+def draws_oracle(G):
+    """oracle_forecast of forecast_cases.draws_case(G) at the call every draws test makes; computed once per process,
+    read-only."""
+    thetas, states = forecast_cases.draws_case(G)
+    rows, nev = oracle_forecast("sir_subgroups", thetas, states, forecast_cases.DRAWS_H, forecast_cases.DRAWS_R,
+                                forecast_cases.DRAWS_KEY, forecast_cases.DRAWS_FIDX)
+    rows.setflags(write=False)
+    nev.setflags(write=False)
+    return rows, nev
+
+
+def reference_thetas(model, G, thetas):
+    """A flat [D, d] theta array as the reference's thetas ((beta, gamma) pairs for the subgroup models)."""
+    if not model.startswith("sir_subgroups"):
+        return [tuple(t) for t in thetas]
+    return [(t[:-1].reshape(G, G), float(t[-1])) for t in thetas]
+
+
+@functools.lru_cache(maxsize=None)
+@_one_thread
+def sweep_oracle(seed):
+    """oracle_forecast of forecast_cases.sweep_case(seed); computed once per process, read-only."""
+    c = forecast_cases.sweep_case(seed)
+    rows, nev = oracle_forecast(c["model"], reference_thetas(c["model"], c["G"], c["thetas"]), c["states"], c["H"],
+                                c["R"], c["key"], c["filter_index"], c["step"])
+    rows.setflags(write=False)
+    nev.setflags(write=False)
+    return rows, nev
+
+
+def extinct(model, G, rows):
+    """[D, R] bool: nobody infected (SEIR: nor exposed) on the last day."""
+    return rows[:, :, -1][..., forecast_cases.infected_columns(model, G)].sum(axis=-1) == 0

@@ -1,6 +1,7 @@
 """Posterior-predictive forecasts, host side (no device): the entry points exist through every layer, the
 histogram-to-quantile step is numpy's inverted-CDF rule, the forecast's row rule is the reference's traj_inf rule
-(tests/pred_tmps.py:55-64) on oracle paths, and bad arguments raise before any context is created."""
+(tests/pred_tmps.py:55-64) on oracle paths, bad arguments raise before any context is created, and the cases of
+tests/forecast_cases.py hold on the oracle what the device tests need them to hold."""
 import os
 import re
 
@@ -9,7 +10,8 @@ import pytest
 
 import oracle
 from conftest import REPO
-from forecast_helpers import bin_rows, traj_inf_rows
+from forecast_cases import DRAWS_GS, DRAWS_H, DRAWS_R, INSTANCES, SWEEP_SEEDS, draws_case, infected_columns, sweep_case
+from forecast_helpers import bin_rows, draws_oracle, extinct, sweep_oracle, traj_inf_rows
 
 
 def test_entry_points_exist_in_every_layer():
@@ -132,3 +134,51 @@ def test_bad_arguments_raise_before_any_context():
     with pytest.raises(ValueError, match="thetas for"):
         epipf.forecast_from_chain("sir", th, np.zeros((4, 3, 3)), 5)
     assert engine._CACHE == cached                            # no context was created
+
+
+# ----------------------------------------------------- what tests/test_gpu_forecast_draws.py's cases hold (oracle only)
+@pytest.mark.parametrize("G", DRAWS_GS)
+def test_draws_case_holds_its_fate_mix(G):
+    """draws_oracle's oracle_forecast also asserts that no path has an event at exactly t = H."""
+    thetas, states = draws_case(G)
+    rows, nev = draws_oracle(G)
+    D, R = nev.shape
+    assert (D, R) == (7, DRAWS_R) and rows.shape == (7, DRAWS_R, DRAWS_H, 3 * G)
+    gone = extinct("sir_subgroups", G, rows).sum(axis=1)
+    infected0 = states[:, 1::3].sum(axis=1)
+    assert infected0[1] == 0 and nev[1].sum() == 0                   # nobody infected: no event
+    assert list(states[2, 1::3]) == [1] + [0] * (G - 1)              # a single infected person, in group 0
+    assert infected0[-1] > 0 and nev[-1].sum() == 0 and not np.any(thetas[-1][0]) and thetas[-1][1] == 0.0
+    assert np.any((gone > 0) & (gone < R))                           # a draw with both fates among its replicates
+    if G >= 3:
+        assert np.any((gone == 0) & (nev.sum(axis=1) > 0))           # a live draw without extinction
+    live = [d for d in range(D) if nev[d].sum() > 0]
+    assert len(live) >= 4
+    for i, a in enumerate(live):                                     # no two live draws could stand in for each other
+        for b in live[i + 1:]:
+            assert not np.array_equal(rows[a], rows[b]), (a, b)
+            assert not np.array_equal(thetas[a][0], thetas[b][0]) and not np.array_equal(states[a], states[b])
+
+
+def test_sweep_cases_hold_their_mix():
+    cases = [sweep_case(s) for s in SWEEP_SEEDS]
+    launched = [(c["model"], c["G"]) for c in cases]
+    assert all(launched.count(inst) >= 2 for inst in INSTANCES)      # every kernel instance at least twice
+    fates = set()
+    for s, c in zip(SWEEP_SEEDS, cases):
+        assert c["D"] * c["R"] <= 6500 and 0 <= c["key"] < 2**63 and 0 <= c["filter_index"] < 2**32
+        assert 0 <= c["step"] < 2**24 and c["states"].min() >= 0 and c["states"].max() <= 60
+        rows, nev = sweep_oracle(s)                                  # asserts: no event at exactly t = H
+        gone = extinct(c["model"], c["G"], rows).sum(axis=1)
+        fates |= {"all" if g == c["R"] else "none" if g == 0 else "mixed" for g in gone}
+    assert fates == {"all", "none", "mixed"}
+    lanes = [c["D"] * c["R"] for c in cases]
+    assert min(lanes) < 64 and max(lanes) > 256                      # less than a wave; more than one 256-lane block
+    assert any(n > 256 and n % 256 for n in lanes)                   # a partial last block
+    assert any(c["R"] % 64 == 0 for c in cases)                      # wave-uniform draws
+    assert any(c["R"] % 64 and c["D"] > 1 and c["D"] * c["R"] > 64 for c in cases)   # draws sharing waves
+    assert any(c["filter_index"] >= 2**31 for c in cases) and any(c["step"] >= 2**16 for c in cases)
+    idle = sum(int(np.sum(c["states"][:, infected_columns(c["model"], c["G"])].sum(axis=1) == 0)) for c in cases)
+    frozen = sum(int(np.sum(~c["thetas"].any(axis=1))) for c in cases)
+    draws = sum(c["D"] for c in cases)
+    assert 0.08 * draws < idle < 0.25 * draws and 0.08 * draws < frozen < 0.25 * draws

@@ -56,7 +56,10 @@ EDGES = [(T, N, C, how)
          for T, N, C, how in [(5, 1, 3, "random"), (5, 63, 3, "random"), (5, 64, 4, "random"), (5, 65, 6, "random"),
                               (4, THREADS + 1, 3, "random"), (1, 70, 3, "random"), (2, 70, 15, "random"),
                               (6, 130, 3, "last"), (6, 130, 4, "identity"), (6, 130, 6, "permutation"),
-                              (3, 2 * THREADS + 7, 15, "permutation")]]
+                              (3, 2 * THREADS + 7, 15, "permutation"),
+                              # G = 8 histories have C = 24; C = 64 is kSmoothMaxC, and with N = 1 the workgroup is one
+                              # wave in which every thread owns a compartment's sum
+                              (3, 70, 24, "random"), (2, 1, 64, "random")]]
 
 
 @pytest.mark.parametrize("T,N,C,how", EDGES)
@@ -315,5 +318,33 @@ def test_state_and_argument_errors(datasets_golden):
         hid[0, 1, 2, 1] = -3
         with pytest.raises(_lib.EpipfError, match="non-negative"):
             eng.smooth_history(hid, anc, 1, 0, q, 5)
+    finally:
+        eng.close()
+
+
+def test_more_compartments_than_the_workgroup_sums_are_refused():
+    """kSmoothMaxC = 64 compartments are the kernel's LDS sums: 64 run (EDGES), 65 are EPIPF_EINVAL."""
+    from epipf import _lib
+    from epipf.engine import Engine
+    L = _lib.load()
+    eng = Engine("sir", 1, 1, 1, 1)
+    try:
+        q = np.array([0.5])
+        for C, want in ((64, _lib.OK), (65, _lib.EINVAL)):
+            hid = np.ones((1, 2, 4, C), dtype=np.int32)
+            anc = np.zeros((1, 2, 4), dtype=np.int32)
+            sums = np.zeros((1, 2, C), dtype=np.int64)
+            qo = np.zeros((1, 1, 2, C), dtype=np.int32)
+            lin = np.zeros((1, 2), dtype=np.int32)
+            rc = L.epipf_smooth_history(eng._h, 1, 2, 4, C, _lib.ptr(hid), _lib.ptr(anc), 1, 0, _lib.ptr(q), 1, 5,
+                                        _lib.ptr(sums), _lib.ptr(qo), _lib.ptr(lin))
+            assert rc == want, C
+            if want == _lib.OK:
+                assert np.all(sums == 4) and np.all(qo == 1)
+            else:
+                assert b"at most 64 compartments" in L.epipf_last_error()
+                assert not sums.any()
+        with pytest.raises(_lib.EpipfError, match="at most 64 compartments"):
+            eng.smooth_history(np.ones((1, 2, 4, 65), dtype=np.int32), np.zeros((1, 2, 4), dtype=np.int32), 1, 0, q, 5)
     finally:
         eng.close()
