@@ -28,6 +28,7 @@
  *                        generation (proposals from the previous weighted population) and its weight denominators
  *   epipf_if2            no reference counterpart (its PMCMC scripts start from hand-tuned runs): iterated filtering, a
  *                        maximum-likelihood search by filters whose particles each carry and jitter their own theta
+ *   epipf_iterated_filtering_subgroups   the same search for the subgroup models at G = 2..4 (theta = beta[G][G], gamma)
  *
  * The host wrapper (stochastic-epidemic-modelling_amd/epipf/) binds these with ctypes and keeps
  * the reference's Python signatures.  Conventions:
@@ -286,13 +287,26 @@ int epipf_abc_smc_weights(epipf_ctx* ctx, const double* theta, int n, const doub
  * iteration found it, its mean_out / log_zetas_out rows from that iteration on are NaN, and the other searches are not
  * affected.  T == 1 is valid (only the step-0 jitter runs).  Every launch of the call is enqueued without host
  * synchronisation.  Afterwards epipf_copy_history / epipf_path_sample / epipf_smooth see the last executed pass of each
- * search.  EPIPF_EINVAL on a subgroup context: those models are out of scope.
+ * search.  EPIPF_EINVAL on a subgroup context: epipf_iterated_filtering_subgroups runs those models.
  * epipf_get_stats afterwards: resample_fallbacks of this call, and at EPIPF_PROFILE_COUNTERS its events,
  * lane_iterations, wave_lane_slots, ssa_exact_lanes and ssa_exact_waves (a failed iteration's steps before the dying one
  * included).  The device counters are left cleared: the next epipf_run reports its own counts only. */
 int epipf_if2(epipf_ctx* ctx, int n_searches, int iterations, double* swarm_inout, int d, const double* half_widths,
               int obs_model, const double* probs, const uint64_t* keys, const uint32_t* filter_index0,
               double* log_zetas_out, double* mean_out, int32_t* iterations_done_out, int32_t* status_out);
+
+/* epipf_if2 for the subgroup models (EPIPF_SIR_SUBGROUPS, EPIPF_SIR_SUBGROUPS2) with 2 <= G <= 4 groups (DESIGN.md
+ * §17.1).  The definition above holds word for word with d = G*G + 1 and theta laid out as beta[G][G] row-major, then
+ * gamma (epipf_run's layout): component c draws from block c / 2, so d = 5 and d = 17 use the first half of their last
+ * block only.  A half-width of 0 leaves a component bit-identical, which fixes entries of the contact matrix (for
+ * example off-diagonals at 0).  EPIPF_SIR_SUBGROUPS2 weighs the sums over the groups, as its filter does.  Arguments,
+ * returns, status, statistics and what the history calls see afterwards are epipf_if2's.  EPIPF_EINVAL on a SIR or SEIR
+ * context (epipf_if2 runs those) and on G = 1 or G > 4: the wider models read their rates by wave-uniform address,
+ * which a per-particle theta is not. */
+int epipf_iterated_filtering_subgroups(epipf_ctx* ctx, int n_searches, int iterations, double* swarm_inout, int d,
+                                       const double* half_widths, int obs_model, const double* probs,
+                                       const uint64_t* keys, const uint32_t* filter_index0, double* log_zetas_out,
+                                       double* mean_out, int32_t* iterations_done_out, int32_t* status_out);
 
 /* The device's restatement of glibc's log (the reference's math.log / numpy legacy exponential),
  * evaluated on the host CPU with the same code and table: out[i] = log(x[i]) bit for bit for normal x[i] > 0.

@@ -21,6 +21,7 @@
 #include "../../include/epipf.h"
 #include "abc_device.hpp"
 #include "epipf_if2.hpp"
+#include "epipf_if2_sub.hpp"
 #include "epipf_internal.hpp"
 #include "epipf_smooth.hpp"
 
@@ -445,6 +446,11 @@ int epipf_create(epipf_ctx** out, int device, int model, int groups, int n_parti
     c->wstride = (size_t)c->B * c->wg;
     // block sums for the lane-group runs' 16-particle blocks too (pick_block, kGroupBlock)
     c->bstride = std::max((size_t)c->B, (size_t)((n_particles + kGroupBlock - 1) / kGroupBlock));
+    // and for the 64-particle one-wave blocks that iterated filtering forces at every model (if2_impl: wg = 64,
+    // lanes = 1), whatever default_wg and the lane-group runs pick; today default_wg is 64, so these change nothing
+    const size_t B64 = ((size_t)n_particles + 63) / 64;
+    c->wstride = std::max(c->wstride, B64 * 64);
+    c->bstride = std::max(c->bstride, B64);
     int rc = 0;
     if (hipSetDevice(device) != hipSuccess) { free_ctx(c); return fail(EPIPF_EHIP, "hipSetDevice(%d) failed", device); }
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -1141,15 +1147,13 @@ int epipf_smooth_history(epipf_ctx* c, int n, int T, int N, int C, const int32_t
     return smooth_run(c, n, T, N, C, hidden, ancestry, lineage, kind, q, n_q, bins, sums_out, quant_out, lineages_out);
 }
 
-// Iterated filtering (DESIGN.md §17): M passes of the filter with theta per particle, all enqueued at once.
-int epipf_if2(epipf_ctx* c, int n_searches, int iterations, double* swarm_inout, int d, const double* half_widths,
-              int obs_model, const double* probs, const uint64_t* keys, const uint32_t* filter_index0,
-              double* log_zetas_out, double* mean_out, int32_t* iterations_done_out, int32_t* status_out) {
-    if (!c || !swarm_inout || !half_widths || !probs || !keys || !filter_index0 || !mean_out || !iterations_done_out ||
-        !status_out)
-        return fail(EPIPF_EINVAL, "NULL argument");
-    if (c->model != EPIPF_SIR && c->model != EPIPF_SEIR)
-        return fail(EPIPF_EINVAL, "iterated filtering covers the SIR and SEIR models; the subgroup models are out of its scope");
+// Iterated filtering (DESIGN.md §17, §17.1): M passes of the filter with theta per particle, all enqueued at once.
+// epipf_if2 (SIR, SEIR) and epipf_iterated_filtering_subgroups (the subgroup models at G <= kMaxLaneG) are this
+// function behind their own model checks; only the launcher differs.
+static int if2_impl(epipf_ctx* c, bool subgroups, int n_searches, int iterations, double* swarm_inout, int d,
+                    const double* half_widths, int obs_model, const double* probs, const uint64_t* keys,
+                    const uint32_t* filter_index0, double* log_zetas_out, double* mean_out,
+                    int32_t* iterations_done_out, int32_t* status_out) {
     if (!c->have_Y) return fail(EPIPF_ESTATE, "epipf_set_observations was not called");
     if (!c->have_pop) return fail(EPIPF_ESTATE, "epipf_set_population was not called");
     const int S = n_searches, M = iterations, N = c->N, T = c->T;
@@ -1198,7 +1202,7 @@ int epipf_if2(epipf_ctx* c, int n_searches, int iterations, double* swarm_inout,
 
     If2Args a{};
     StepArgs& s = a.s;
-    s.N = N; s.T = T; s.max_chains = c->max_chains; s.wg = 64; s.B = c->B; s.lanes = 1; s.lane_events = 1;
+    s.N = N; s.T = T; s.max_chains = c->max_chains; s.wg = 64; s.B = (N + 63) / 64; s.lanes = 1; s.lane_events = 1;
     s.resample_mode = EPIPF_RESAMPLE_MULTINOMIAL; s.lf_max = c->lf_max;
     s.count_events = c->profiling >= EPIPF_PROFILE_COUNTERS ? 1 : 0;
     s.hist_stride = c->hist_stride; s.anc_stride = c->anc_stride; s.wstride = c->wstride; s.bstride = c->bstride;
@@ -1222,7 +1226,8 @@ int epipf_if2(epipf_ctx* c, int n_searches, int iterations, double* swarm_inout,
         HIP_TRY(hipStreamWaitEvent(c->aux[g], c->fork, 0));
     }
     c->last_groups = fs.n;
-    hipError_t le = launch_if2(a, c->model, obs_model, S, half_widths, fs);
+    hipError_t le = subgroups ? launch_if2_sub(a, c->model, c->G, obs_model, S, half_widths, fs)
+                              : launch_if2(a, c->model, obs_model, S, half_widths, fs);
     if (le != hipSuccess) return fail(EPIPF_EHIP, "kernel launch failed: %s", hipGetErrorString(le));
     std::vector<double> lz((size_t)M * mc * T), mean((size_t)S * M * d);
     HIP_TRY(hipMemcpyAsync(soa.data(), d_start, sizeof(double) * soa.size(), hipMemcpyDeviceToHost, c->stream));
@@ -1268,6 +1273,37 @@ int epipf_if2(epipf_ctx* c, int n_searches, int iterations, double* swarm_inout,
     c->have_run = true;
     trim_scratch(c);
     return EPIPF_OK;
+}
+
+int epipf_if2(epipf_ctx* c, int n_searches, int iterations, double* swarm_inout, int d, const double* half_widths,
+              int obs_model, const double* probs, const uint64_t* keys, const uint32_t* filter_index0,
+              double* log_zetas_out, double* mean_out, int32_t* iterations_done_out, int32_t* status_out) {
+    if (!c || !swarm_inout || !half_widths || !probs || !keys || !filter_index0 || !mean_out || !iterations_done_out ||
+        !status_out)
+        return fail(EPIPF_EINVAL, "NULL argument");
+    if (c->model != EPIPF_SIR && c->model != EPIPF_SEIR)
+        return fail(EPIPF_EINVAL, "iterated filtering covers the SIR and SEIR models; the subgroup models are out of its scope "
+                                  "(epipf_iterated_filtering_subgroups runs them at G <= %d)", kMaxLaneG);
+    return if2_impl(c, false, n_searches, iterations, swarm_inout, d, half_widths, obs_model, probs, keys, filter_index0,
+                    log_zetas_out, mean_out, iterations_done_out, status_out);
+}
+
+// The subgroup models' entry point: theta = beta[G][G] row-major then gamma, d = G*G + 1, G <= 4.
+// G = 5..8 read their rates through WideParam by wave-uniform address, which a per-particle theta is not.
+int epipf_iterated_filtering_subgroups(epipf_ctx* c, int n_searches, int iterations, double* swarm_inout, int d,
+                                       const double* half_widths, int obs_model, const double* probs,
+                                       const uint64_t* keys, const uint32_t* filter_index0, double* log_zetas_out,
+                                       double* mean_out, int32_t* iterations_done_out, int32_t* status_out) {
+    if (!c || !swarm_inout || !half_widths || !probs || !keys || !filter_index0 || !mean_out || !iterations_done_out ||
+        !status_out)
+        return fail(EPIPF_EINVAL, "NULL argument");
+    if (c->model != EPIPF_SIR_SUBGROUPS && c->model != EPIPF_SIR_SUBGROUPS2)
+        return fail(EPIPF_EINVAL, "epipf_iterated_filtering_subgroups covers the subgroup models; epipf_if2 runs SIR and SEIR");
+    if (c->G < 2 || c->G > kMaxLaneG)
+        return fail(EPIPF_EINVAL, "iterated filtering of the subgroup models needs 2 <= G <= %d groups, this context has %d",
+                    kMaxLaneG, c->G);
+    return if2_impl(c, true, n_searches, iterations, swarm_inout, d, half_widths, obs_model, probs, keys, filter_index0,
+                    log_zetas_out, mean_out, iterations_done_out, status_out);
 }
 
 int epipf_glibc_log(int64_t n, const double* x, double* out) {

@@ -31,4 +31,8 @@ struct If2Args {
 hipError_t launch_if2(const If2Args& a, int model, int obs, int n_searches, const double* half_widths,
                       const FilterStreams& fs);
 
+// The end-of-iteration reduction (if2_finish_kernel) of a.m for the n_g searches from a.s.chain0 on, enqueued on st; it
+// reads a.d, so it serves every model's swarm (epipf_if2_sub.hip).
+void launch_if2_finish(const If2Args& a, int n_g, hipStream_t st);
+
 }  // namespace epipf

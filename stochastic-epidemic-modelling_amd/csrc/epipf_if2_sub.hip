@@ -1,18 +1,14 @@
-// epipf_if2.hip -- the iterated-filtering kernels for MI355X (gfx950) and their launcher.
+// epipf_if2_sub.hip -- the iterated-filtering kernels of the subgroup models (G = 2..4) for MI355X (gfx950) and their
+// launcher.
 //
-// if2_init_kernel / if2_step_kernel are pf_init_kernel / pf_step_kernel (epipf_kernels.hpp) with theta per particle:
-// one lane per particle, one wave per block, the same grid (step_block), weights (particle_weight), scans
-// (scan_block_sums / scan_segments / block_inclusive_scan) and certified resampling search.  What differs:
-//   - the filter index is the chain's plus the iteration (cp.f + m), so the M passes of a call need no upload between;
-//   - after the ancestor is known the lane gathers the ancestor's theta, jitters it (perturb) and stores it, and
-//     runs the SSA on its own ChainParam copy with that theta (rates in VGPRs instead of SGPRs);
-//   - the SSA is the certified f32 loop (fast_propagate) with the exact loop per lane for what it hands back.  The
-//     wave-cooperative replay (coop_replay) takes one wave-uniform ChainParam, which a lane's theta is not;
-//   - with count_events the step kernel adds to pf_step_kernel's counter slots (events, lane and wave iterations, exact
-//     particle-steps and their waves), which epipf_if2 harvests and clears.
-// if2_finish_kernel closes an iteration of the searches still running: the swarm becomes the next iteration's start
-// and its component means are reduced in a fixed order.
-#include "epipf_if2.hpp"
+// if2_sub_init_kernel / if2_sub_step_kernel are if2_init_kernel / if2_step_kernel (epipf_if2.hip) with G groups: one lane
+// per particle, one wave per block, the filter's grid, weights, scans and certified resampling search.  theta is
+// beta[G][G] row-major then gamma, D = G*G + 1 components per particle: gathered from the ancestor out of the
+// component-major swarm, jittered on domain 7 << 24 (component c from block c / 2), stored, and used as the lane's own
+// rates (a per-lane ChainParam copy: theta for the exact loop, thetaf for the certified f32 loop).  The loops over the
+// components are fully unrolled so that the rates stay in registers (FastSubgroups reads them through a pointer).  No
+// wave-cooperative replay: it takes one wave-uniform ChainParam.  The end-of-iteration reduction is if2_finish_kernel.
+#include "epipf_if2_sub.hpp"
 
 #include <algorithm>
 
@@ -23,7 +19,8 @@ namespace epipf {
 // theta[c] + hw[c] (2u - 1), reflected at 0; component c draws from block c / 2 of (., j, tag, f): words (0, 1) for
 // even c, (2, 3) for odd c.  No contraction (-ffp-contract=off): the restatement's roundings.
 template <int D>
-__device__ __forceinline__ void if2_perturb(double* th, const If2Args& a, uint32_t j, uint32_t tag, const ChainParam& cp) {
+__device__ __forceinline__ void if2_sub_perturb(double* th, const If2SubArgs& a, uint32_t j, uint32_t tag,
+                                                const ChainParam& cp) {
 #pragma unroll
     for (int b = 0; b < (D + 1) / 2; ++b) {
         const Block r = philox((uint32_t)b, j, tag, cp.f, cp.k0, cp.k1);
@@ -40,10 +37,11 @@ __device__ __forceinline__ void if2_perturb(double* th, const If2Args& a, uint32
     }
 }
 
-template <int MODEL, int OBS>
-__global__ __launch_bounds__(64) void if2_init_kernel(If2Args a) {
-    constexpr int C = Shape<MODEL, 1>::C;
-    constexpr int D = (MODEL == kSIR) ? 2 : 3;
+template <int MODEL, int G, int OBS>
+__global__ __launch_bounds__(64) void if2_sub_init_kernel(If2SubArgs a) {
+    static_assert(MODEL >= kSubgroups && G >= 2 && G <= kMaxLaneG, "the subgroup models with per-lane rates");
+    constexpr int C = Shape<MODEL, G>::C;
+    constexpr int D = G * G + 1;
     constexpr int WG = 64;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const StepArgs& s = a.s;
@@ -62,7 +60,7 @@ __global__ __launch_bounds__(64) void if2_init_kernel(If2Args a) {
 #pragma unroll
     for (int c = 0; c < C; ++c) x[c] = 0.0;
     if (j < s.N) {
-        init_particle<MODEL, 1>(s, cp, j, x);                            // pmcmc.py:156-175
+        init_particle<MODEL, G>(s, cp, j, x);                            // pmcmc.py:156-175
         int32_t* h = s.hidden + (size_t)chain * s.hist_stride + (size_t)j * C;
 #pragma unroll
         for (int c = 0; c < C; ++c) h[c] = (int32_t)x[c];
@@ -70,7 +68,7 @@ __global__ __launch_bounds__(64) void if2_init_kernel(If2Args a) {
         double th[D];
 #pragma unroll
         for (int c = 0; c < D; ++c) th[c] = a.start[((size_t)chain * D + c) * s.N + j];
-        if2_perturb<D>(th, a, (uint32_t)j, kDomainIf2, cp);              // step 0
+        if2_sub_perturb<D>(th, a, (uint32_t)j, kDomainIf2, cp);          // step 0
 #pragma unroll
         for (int c = 0; c < D; ++c) a.swarm[((size_t)chain * D + c) * s.N + j] = th[c];   // buffer 0
     }
@@ -78,7 +76,7 @@ __global__ __launch_bounds__(64) void if2_init_kernel(If2Args a) {
     if (s.T > 1) {
         double w = 0.0;
         if (j < s.N)
-            w = particle_weight<MODEL, 1, OBS>(x, s.Y, cp, s.cp + chain, s.lf, s.lf_max,
+            w = particle_weight<MODEL, G, OBS>(x, s.Y, cp, s.cp + chain, s.lf, s.lf_max,
                                                s.hidden + (size_t)chain * s.hist_stride + (size_t)j * C);
         const size_t wbase = (size_t)chain * s.wstride;                  // buffer 0
         const double loc = block_inclusive_scan<WG>(w, smem);
@@ -88,12 +86,14 @@ __global__ __launch_bounds__(64) void if2_init_kernel(If2Args a) {
     }
 }
 
-template <int MODEL, int OBS>
-__global__ __launch_bounds__(64) void if2_step_kernel(If2Args a, int p) {
-    constexpr int C = Shape<MODEL, 1>::C;
-    constexpr int K = Shape<MODEL, 1>::K;
-    constexpr int D = (MODEL == kSIR) ? 2 : 3;
+template <int MODEL, int G, int OBS>
+__global__ __launch_bounds__(64) void if2_sub_step_kernel(If2SubArgs a, int p) {
+    static_assert(MODEL >= kSubgroups && G >= 2 && G <= kMaxLaneG, "the subgroup models with per-lane rates");
+    constexpr int C = Shape<MODEL, G>::C;
+    constexpr int K = Shape<MODEL, G>::K;
+    constexpr int D = G * G + 1;
     constexpr int WG = 64;
+    static_assert(D <= kLaneTheta, "ChainParam::theta holds the lane's rates");
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const StepArgs& s = a.s;
     LogTab* tab = reinterpret_cast<LogTab*>(smem);       // the layout of pf_step_kernel (step_lds_bytes)
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(64) void if2_step_kernel(If2Args a, int p) {
         }
     }
     // the ancestor's theta, jittered: this particle's rates.  The lane's own ChainParam copy differs from the chain's
-    // in theta and thetaf only.
+    // in theta and thetaf only.  Lanes past N keep the chain's zeroed theta and run no SSA.
     double x[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) x[c] = 0.0;
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(64) void if2_step_kernel(If2Args a, int p) {
         double th[D];
 #pragma unroll
         for (int c = 0; c < D; ++c) th[c] = a.swarm[(((size_t)prev * s.max_chains + chain) * D + c) * s.N + anc];
-        if2_perturb<D>(th, a, (uint32_t)j, ((uint32_t)p & 0xFFFFFFu) | kDomainIf2, cp);
+        if2_sub_perturb<D>(th, a, (uint32_t)j, ((uint32_t)p & 0xFFFFFFu) | kDomainIf2, cp);
 #pragma unroll
         for (int c = 0; c < D; ++c) {
             a.swarm[(((size_t)cur * s.max_chains + chain) * D + c) * s.N + j] = th[c];
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(64) void if2_step_kernel(If2Args a, int p) {
         const int32_t* hp = s.hidden + (size_t)chain * s.hist_stride + ((size_t)(p - 1) * s.N + anc) * C;
 #pragma unroll
         for (int c = 0; c < C; ++c) x[c] = (double)hp[c];
-        fast_ok = fast_propagate<MODEL, 1>(x, lcp, (uint32_t)j, ptag, 1.0, nev, iters, eligible);
+        fast_ok = fast_propagate<MODEL, G>(x, lcp, (uint32_t)j, ptag, 1.0, nev, iters, eligible);
     }
     // lanes the f32 loop could not run or could not certify at the step boundary: the exact loop from the untouched
     // parent state, per lane.  Its log table goes to LDS only in waves that need it (one wave per block, so the test
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(64) void if2_step_kernel(If2Args a, int p) {
     if (__any(!fast_ok)) {
         for (int i = tid; i < kLogTabEntries; i += WG) tab[i] = s.logtab[i];
         __syncthreads();
-        if (!fast_ok) nev = exact_propagate<MODEL, 1>(x, lcp, (uint32_t)j, ptag, 1.0, tab, iters);
+        if (!fast_ok) nev = exact_propagate<MODEL, G>(x, lcp, (uint32_t)j, ptag, 1.0, tab, iters);
     }
     if (s.count_events) {  // pf_step_kernel's counters, before the weights so that nev and iters die here
         unsigned long long e = (unsigned long long)nev, li = (unsigned long long)iters;
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(64) void if2_step_kernel(If2Args a, int p) {
         int32_t* hc = s.hidden + (size_t)chain * s.hist_stride + ((size_t)p * s.N + j) * C;
 #pragma unroll
         for (int c = 0; c < C; ++c) hc[c] = (int32_t)x[c];
-        if (p + 1 < s.T) w = particle_weight<MODEL, 1, OBS>(x, s.Y + (size_t)p * K, cp, s.cp + chain, s.lf, s.lf_max, hc);
+        if (p + 1 < s.T) w = particle_weight<MODEL, G, OBS>(x, s.Y + (size_t)p * K, cp, s.cp + chain, s.lf, s.lf_max, hc);
     }
     if (p + 1 < s.T) {
         const double loc = block_inclusive_scan<WG>(w, red);
@@ -215,44 +215,15 @@ __global__ __launch_bounds__(64) void if2_step_kernel(If2Args a, int p) {
     }
 }
 
-// End of iteration m for the searches still running: block (c, search) copies component c of the final swarm (buffer
-// (T - 1) & 1) to the start copy and reduces its mean: each thread's strided partial sum, then the 256 partials in
-// thread order by one thread (a fixed order: the same bits on every run).
-__global__ __launch_bounds__(256) void if2_finish_kernel(If2Args a) {
-    __shared__ double part[256];
-    const StepArgs& s = a.s;
-    const int c = blockIdx.x, chain = s.chain0 + (int)blockIdx.y;
-    if (s.status[chain] != 0) return;
-    const int last = (s.T - 1) & 1;
-    const double* src = a.swarm + (((size_t)last * s.max_chains + chain) * a.d + c) * s.N;
-    double* dst = a.start + ((size_t)chain * a.d + c) * s.N;
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < s.N; i += 256) {
-        const double v = src[i];
-        dst[i] = v;
-        acc = acc + v;
-    }
-    part[threadIdx.x] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double tot = 0.0;
-        for (int i = 0; i < 256; ++i) tot = tot + part[i];
-        a.mean[((size_t)chain * a.M + a.m) * a.d + c] = tot / (double)s.N;
-        if (c == 0) a.done[chain] = a.m + 1;
-    }
-}
-
-void launch_if2_finish(const If2Args& a, int n_g, hipStream_t st) {
-    hipLaunchKernelGGL(if2_finish_kernel, dim3(a.d, n_g), dim3(256), 0, st, a);
-}
-
-template <int MODEL, int OBS>
-static hipError_t launch_if2_t(const If2Args& a, int n_searches, const double* half_widths, const FilterStreams& fs) {
+template <int MODEL, int G, int OBS>
+static hipError_t launch_if2_sub_t(const If2Args& a, int n_searches, const double* half_widths, const FilterStreams& fs) {
     const StepArgs& s0 = a.s;
     const size_t lds = step_lds_bytes(s0.B, 64);
     const int S = std::max(1, std::min(fs.n, n_searches));
     for (int g = 0; g < S; ++g) {
-        If2Args ag = a;
+        If2Args fin = a;                                 // if2_finish_kernel's block: the same layout and buffers
+        If2SubArgs ag{};
+        ag.s = a.s; ag.d = a.d; ag.M = a.M; ag.swarm = a.swarm; ag.start = a.start;
         ag.s.chain0 = (int)((long)n_searches * g / S);
         const int n_g = (int)((long)n_searches * (g + 1) / S) - ag.s.chain0;
         const hipStream_t st = fs.s[g];
@@ -262,9 +233,12 @@ static hipError_t launch_if2_t(const If2Args& a, int n_searches, const double* h
             ag.m = m;
             for (int c = 0; c < a.d; ++c) ag.hw[c] = half_widths[(size_t)m * a.d + c];
             ag.s.log_zeta = s0.log_zeta + (size_t)m * s0.max_chains * s0.T;
-            hipLaunchKernelGGL((if2_init_kernel<MODEL, OBS>), grid, block, lds, st, ag);
-            for (int p = 1; p < s0.T; ++p) hipLaunchKernelGGL((if2_step_kernel<MODEL, OBS>), grid, block, lds, st, ag, p);
-            launch_if2_finish(ag, n_g, st);
+            hipLaunchKernelGGL((if2_sub_init_kernel<MODEL, G, OBS>), grid, block, lds, st, ag);
+            for (int p = 1; p < s0.T; ++p)
+                hipLaunchKernelGGL((if2_sub_step_kernel<MODEL, G, OBS>), grid, block, lds, st, ag, p);
+            fin.s = ag.s;
+            fin.m = m;
+            launch_if2_finish(fin, n_g, st);
         }
         if (g > 0) (void)hipEventRecord(fs.join[g], st);
     }
@@ -272,15 +246,29 @@ static hipError_t launch_if2_t(const If2Args& a, int n_searches, const double* h
     return hipGetLastError();
 }
 
-hipError_t launch_if2(const If2Args& a, int model, int obs, int n_searches, const double* half_widths,
-                      const FilterStreams& fs) {
-    if (a.s.wg != 64 || a.s.lanes != 1 || a.M < 1) return hipErrorInvalidValue;
-    if (model == kSIR && a.d == 2)
-        return obs == kBinomial ? launch_if2_t<kSIR, kBinomial>(a, n_searches, half_widths, fs)
-                                : launch_if2_t<kSIR, kNormal>(a, n_searches, half_widths, fs);
-    if (model == kSEIR && a.d == 3)
-        return obs == kBinomial ? launch_if2_t<kSEIR, kBinomial>(a, n_searches, half_widths, fs)
-                                : launch_if2_t<kSEIR, kNormal>(a, n_searches, half_widths, fs);
+template <int MODEL, int G>
+static hipError_t launch_if2_sub_o(const If2Args& a, int obs, int n_searches, const double* half_widths,
+                                   const FilterStreams& fs) {
+    return obs == kBinomial ? launch_if2_sub_t<MODEL, G, kBinomial>(a, n_searches, half_widths, fs)
+                            : launch_if2_sub_t<MODEL, G, kNormal>(a, n_searches, half_widths, fs);
+}
+
+template <int MODEL>
+static hipError_t launch_if2_sub_g(const If2Args& a, int G, int obs, int n_searches, const double* half_widths,
+                                   const FilterStreams& fs) {
+    switch (G) {
+        case 2: return launch_if2_sub_o<MODEL, 2>(a, obs, n_searches, half_widths, fs);
+        case 3: return launch_if2_sub_o<MODEL, 3>(a, obs, n_searches, half_widths, fs);
+        case 4: return launch_if2_sub_o<MODEL, 4>(a, obs, n_searches, half_widths, fs);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_if2_sub(const If2Args& a, int model, int G, int obs, int n_searches, const double* half_widths,
+                          const FilterStreams& fs) {
+    if (a.s.wg != 64 || a.s.lanes != 1 || a.M < 1 || a.d != G * G + 1 || a.d > kLaneTheta) return hipErrorInvalidValue;
+    if (model == kSubgroups) return launch_if2_sub_g<kSubgroups>(a, G, obs, n_searches, half_widths, fs);
+    if (model == kSubgroups2) return launch_if2_sub_g<kSubgroups2>(a, G, obs, n_searches, half_widths, fs);
     return hipErrorInvalidValue;
 }
 

@@ -168,6 +168,15 @@ class Engine:
         """epipf_if2: iterated filtering from the swarms [S, N, d] with the half-width table [M, d], search s at filter
         indices filter_index0[s] + m.  Returns (swarm [S, N, d], mean [S, M, d], log_zetas [S, M, T],
         iterations_done [S], status [S]); history() afterwards holds each search's last executed pass."""
+        return self._if2("epipf_if2", swarm, half_widths, probs, keys, filter_index0, observations)
+
+    def if2_subgroups(self, swarm, half_widths, probs, keys, filter_index0, observations=False):
+        """epipf_iterated_filtering_subgroups: if2() for the subgroup models at G = 2..4, d = G*G + 1 with theta laid
+        out as beta[G][G] row-major, then gamma.  Arguments and returns as if2()."""
+        return self._if2("epipf_iterated_filtering_subgroups", swarm, half_widths, probs, keys, filter_index0,
+                         observations)
+
+    def _if2(self, entry, swarm, half_widths, probs, keys, filter_index0, observations):
         swarm = np.array(swarm, dtype=np.float64, order="C")          # a copy: the library writes the result into it
         hw = np.ascontiguousarray(np.asarray(half_widths, dtype=np.float64))
         if swarm.ndim != 3 or swarm.shape[1] != self.N:
@@ -185,8 +194,8 @@ class Engine:
         done = np.zeros(S, dtype=np.int32)
         st = np.empty(S, dtype=np.int32)
         obs = _lib.OBS_NORMAL if observations else _lib.OBS_BINOMIAL
-        check(self._L.epipf_if2(self._h, S, M, ptr(swarm), d, ptr(hw), obs, ptr(probs), ptr(keys), ptr(f0), ptr(lz),
-                                ptr(mean), ptr(done), ptr(st)), "epipf_if2")
+        check(getattr(self._L, entry)(self._h, S, M, ptr(swarm), d, ptr(hw), obs, ptr(probs), ptr(keys), ptr(f0),
+                                      ptr(lz), ptr(mean), ptr(done), ptr(st)), entry)
         self._last_n = S
         self._last_status = st.copy()
         _PARTICLE_STEPS[0] += int(np.minimum(done + 1, M).sum()) * self.N * self.T
