@@ -28,11 +28,19 @@ enum Obs : int { kBinomial = 0, kNormal = 1 };
 // Salmon et al. SC'11; constants and key schedule of Random123.  Counter words: (c0, c1, c2, c3).
 struct Block { uint32_t x, y, z, w; };
 
-// INVX: return ~x (the last round's three-way XOR with truth table 0x69 instead of 0x96, no extra instruction);
-// the f32 event loop needs 1 - U, whose low word is ~x.
-template <bool INVX = false>
-__device__ __forceinline__ Block philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                        uint32_t k1) {
+// The block before its last round's two three-way XORs: y and w (the low product words of round 9) and the operands
+// of x = xh ^ xc ^ k0 and z = zh ^ zc ^ k1 (the high product words, round 8's low words, the round-9 keys).  The one-lane
+// SIR loop reads y and w on every event and x and z on rare paths only, and forms them there (one v_bitop3_b32 each,
+// inside the rare block; not_x: truth table 0x69 instead of 0x96, the f32 loop's 1 - U has ~x as its low word).
+struct LazyBlock {
+    uint32_t y, w, xh, xc, zh, zc, k0, k1;
+    __device__ __forceinline__ uint32_t x() const { return __builtin_amdgcn_bitop3_b32(xh, xc, k0, 0x96); }
+    __device__ __forceinline__ uint32_t not_x() const { return __builtin_amdgcn_bitop3_b32(xh, xc, k0, 0x69); }
+    __device__ __forceinline__ uint32_t z() const { return __builtin_amdgcn_bitop3_b32(zh, zc, k1, 0x96); }
+};
+
+__device__ __forceinline__ LazyBlock philox_lazy(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                                 uint32_t k1) {
     // Rounds 0-2 keep plain XORs: with a wave-uniform counter word and key, the compiler runs most of them on
     // the scalar unit.  From round 3 on every word is lane-varying and each three-way XOR is one gfx950
     // v_bitop3_b32 (truth table 0x96) instead of two v_xor_b32: 14 fewer VALU instructions per block.
@@ -51,11 +59,17 @@ __device__ __forceinline__ Block philox(uint32_t c0, uint32_t c1, uint32_t c2, u
         c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
     }
-    constexpr unsigned kLastX = INVX ? 0x69u : 0x96u;               // round 9
-    const uint64_t p0 = (uint64_t)0xD2511F53u * (uint64_t)c0;
+    const uint64_t p0 = (uint64_t)0xD2511F53u * (uint64_t)c0;       // round 9
     const uint64_t p1 = (uint64_t)0xCD9E8D57u * (uint64_t)c2;
-    return Block{(uint32_t)__builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), c1, k0, kLastX), (uint32_t)p1,
-                 (uint32_t)__builtin_amdgcn_bitop3_b32((uint32_t)(p0 >> 32), c3, k1, 0x96), (uint32_t)p0};
+    return LazyBlock{(uint32_t)p1, (uint32_t)p0, (uint32_t)(p1 >> 32), c1, (uint32_t)(p0 >> 32), c3, k0, k1};
+}
+
+// The whole block.  INVX: return ~x for x (no extra instruction).
+template <bool INVX = false>
+__device__ __forceinline__ Block philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                        uint32_t k1) {
+    const LazyBlock b = philox_lazy(c0, c1, c2, c3, k0, k1);
+    return Block{INVX ? b.not_x() : b.x(), b.y, b.z(), b.w};
 }
 
 // 53-bit uniform in [0, 1): ((hi << 32 | lo) >> 11) * 2^-53  (numpy's Philox double convention).
@@ -1226,6 +1240,9 @@ template <int G> struct GroupSsa<kSubgroups2, G> { using type = FastSubgroupsPac
 //            decides, as there, and overwrites s.
 //   exit     df and B are per lane and keep their last values in a lane that has left the loop, so "certainly inside
 //            the step" (df > B) is evaluated once after the loop; a lane that never entered reads as inside.
+//   words    an event reads the block's y and w; z only in the f64 channel's block and x / ~x only in the two small-x
+//            log blocks (0.4% of events), so the last round's two three-way XORs are formed inside those blocks
+//            (LazyBlock) and the main path issues neither.  Same words, bit for bit.
 __device__ __forceinline__ bool fast_propagate_sir(double* x, const ChainParam& cp, uint32_t j, uint32_t ptag,
                                                    double tmax, int& nev_out, int& iters, bool& eligible) {
     using F = FastSsa<kSIR, 1>;
@@ -1240,12 +1257,12 @@ __device__ __forceinline__ bool fast_propagate_sir(double* x, const ChainParam& 
     float R = 0.f, df = 1.f, B = 0.f, s = 1.f;                         // df > B: a lane that never enters is inside
     uint32_t ks = 0;                                                   // event index, wave-uniform (SGPR)
     bool alive = I > 0.f;
-    Block rn{0u, 0u, 0u, 0u};
-    if (alive) rn = philox<true>(0u, j, ptag, cp.f, cp.k0, cp.k1);    // x word inverted: ~x
+    LazyBlock rn{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    if (alive) rn = philox_lazy(0u, j, ptag, cp.f, cp.k0, cp.k1);
     while (alive) {
-        const Block r = rn;
+        const LazyBlock r = rn;                                        // y, w and what x and z are made of
         ks = __builtin_amdgcn_readfirstlane(ks) + 1u;
-        rn = philox<true>(ks, j, ptag, cp.f, cp.k0, cp.k1);
+        rn = philox_lazy(ks, j, ptag, cp.f, cp.k0, cp.k1);
         const float c0 = bNh * (D * I);                                // = bN (S I), FastSsa::cum
         const float total = fmaf(g, I, c0);
         const float ri = __builtin_amdgcn_rcpf(total);
@@ -1255,13 +1272,13 @@ __device__ __forceinline__ bool fast_propagate_sir(double* x, const ChainParam& 
         if (fabsf(t) <= kB) {                                          // too close: the reference expression in f64
             st.S = D * 0.5f;
             st.I = I;
-            s = st.exact_channel(cp, u01(r.z, r.w)) ? -1.0f : 1.0f;
+            s = st.exact_channel(cp, u01(r.z(), r.w)) ? -1.0f : 1.0f;  // z: formed here only
         }
         const uint32_t nh = ~r.y;
         float lg = __builtin_amdgcn_logf((float)nh * 0x1.0p-32f);     // 1 - U from its top word: <= 2 ulp for x >= 2^-8
         if (nh < 0x1000000u) {                                         // 1 - U < 2^-8: 0.4% of events
-            if (nh < 4096u) lg = tiny_log2(~r.x, r.y);                // 1 - U < 2^-20
-            else lg = __builtin_amdgcn_logf(fmaf((float)nh, 0x1.0p-32f, (float)r.x * 0x1.0p-64f));  // r.x is ~x
+            if (nh < 4096u) lg = tiny_log2(r.x(), r.y);               // 1 - U < 2^-20
+            else lg = __builtin_amdgcn_logf(fmaf((float)nh, 0x1.0p-32f, (float)r.not_x() * 0x1.0p-64f));   // ~x
         }
         rem = rem + (double)(lg * ri);                                 // np.random.exponential
         R += ri;
