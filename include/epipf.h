@@ -18,6 +18,8 @@
  *                        the continuous path over [0, H] binned to one row per day, with ensemble sums and histograms
  *   epipf_smooth / epipf_smooth_history   no reference counterpart: the smoothing distribution over the observed window
  *                        (daily means, quantiles, surviving lineages) from the resident history, or from a caller's
+ *   epipf_smooth_lag / epipf_smooth_lag_history   no reference counterpart: the fixed-lag smoother, each day from the
+ *                        particles `lag` days later traced back (lag 1: the filtering distribution)
  *   epipf_resample       pmcmc.py:185-190  normalise + np.random.choice(range(N), N, p=w/sum(w)) with
  *                        caller-supplied uniforms (bit-exact to numpy's legacy choice)
  *   epipf_abc            abc_algo.py:17-109  abc_algo(observed_data, no_of_samples, threshold, priors)
@@ -216,6 +218,21 @@ int epipf_smooth(epipf_ctx* ctx, int n_chains, int lineage, int kind, const doub
 int epipf_smooth_history(epipf_ctx* ctx, int n, int T, int N, int C, const int32_t* hidden, const int32_t* ancestry,
                          int lineage, int kind, const double* q, int n_q, int bins, int64_t* sums_out,
                          int32_t* quant_out, int32_t* lineages_out);
+
+/* Fixed-lag smoother (Kitagawa 1996): day p estimated from the particles of day
+ * e(p) = min(p + lag, T-1) traced back to day p, with the same history, `lineage`, outputs and quantile rule as above:
+ *   w[e(p)][i] = 1;  w[q][i] = sum of w[q+1][j] over the j with a[q+shift][j] == i  (q = e(p)-1 .. p);  m[p] = w[p]
+ *   sums[p][c] = sum_i m[p][i] h[p][i][c];  lineages[p] = #{i : m[p][i] > 0};  sum_i m[p][i] = N on every day
+ * lag == 0 is EPIPF_SMOOTH_PREDICTIVE and lag >= T-1 is EPIPF_SMOOTH_SMOOTHING, bit for bit; lag == 1 with
+ * EPIPF_LINEAGE_GENEALOGY is the filtering distribution (the resampled parents); lineages[p] does not increase with
+ * lag.  lag < 0 is EPIPF_EINVAL; every other rule (state, n, q, bins, C <= 64, the histogram cap, the contents of
+ * hidden and ancestry, chains that did not run, slicing under the scratch budget) is epipf_smooth's and
+ * epipf_smooth_history's.  Each (chain, day) is one workgroup's window, so one chain occupies up to T compute units. */
+int epipf_smooth_lag(epipf_ctx* ctx, int n_chains, int lineage, int lag, const double* q, int n_q, int bins,
+                     int64_t* sums_out, int32_t* quant_out, int32_t* lineages_out);
+int epipf_smooth_lag_history(epipf_ctx* ctx, int n, int T, int N, int C, const int32_t* hidden, const int32_t* ancestry,
+                             int lineage, int lag, const double* q, int n_q, int bins, int64_t* sums_out,
+                             int32_t* quant_out, int32_t* lineages_out);
 
 /* Standalone resampler: out[j] = numpy legacy choice(range(n), n, p=w/sum(w)) given uniforms u[j].
  * Returns EPIPF_STATUS_DEGENERATE (as a positive value) where numpy raises ValueError. */

@@ -24,6 +24,7 @@
 #include "epipf_if2_sub.hpp"
 #include "epipf_internal.hpp"
 #include "epipf_smooth.hpp"
+#include "epipf_smooth_lag.hpp"
 
 using namespace epipf;
 
@@ -1032,11 +1033,15 @@ int epipf_forecast(epipf_ctx* c, int n_draws, int replicates, int horizon, const
 constexpr size_t kSmoothHistLimit = (size_t)256 << 20;
 constexpr size_t kSmoothScratch = (size_t)4 << 30;
 
+constexpr int kSmoothNoLag = -1;
+
 // The smoother over n chains of [T][N][C] histories: the context's own (up_hidden == NULL: its strides and the last
-// run's status) or the caller's host arrays, uploaded to scratch.
+// run's status) or the caller's host arrays, uploaded to scratch.  lag >= 0 is the fixed-lag pass (§16.1, `kind` is
+// EPIPF_SMOOTH_SMOOTHING): one workgroup per (chain, day), the days of a chain sliced too when its global rows alone
+// exceed the budget; lag >= T - 1 is the smoother itself and runs as it.
 static int smooth_run(epipf_ctx* c, int n, int T, int N, int C, const int32_t* up_hidden, const int32_t* up_ancestry,
-                      int lineage, int kind, const double* q, int n_q, int bins, int64_t* sums_out, int32_t* quant_out,
-                      int32_t* lineages_out) {
+                      int lineage, int kind, int lag, const double* q, int n_q, int bins, int64_t* sums_out,
+                      int32_t* quant_out, int32_t* lineages_out) {
     if (!sums_out || !lineages_out) return fail(EPIPF_EINVAL, "NULL argument");
     if (lineage != EPIPF_LINEAGE_REFERENCE && lineage != EPIPF_LINEAGE_GENEALOGY)
         return fail(EPIPF_EINVAL, "unknown lineage %d", lineage);
@@ -1055,12 +1060,23 @@ static int smooth_run(epipf_ctx* c, int n, int T, int N, int C, const int32_t* u
     const bool predictive = kind == EPIPF_SMOOTH_PREDICTIVE;
     bool lds_rows = N <= kSmoothLdsMaxN;
     if (const char* e = getenv("EPIPF_SMOOTH_LDS")) lds_rows = lds_rows && atoi(e) != 0;
-    const size_t mb1 = (predictive || lds_rows) ? 0 : 2 * sizeof(uint32_t) * (size_t)N;   // one chain's global rows
+    const bool lagged = lag >= 0 && lag < T - 1;
+    const size_t rb1 = (predictive || lds_rows) ? 0 : 2 * sizeof(uint32_t) * (size_t)N;   // one workgroup's global rows
     size_t budget = kSmoothScratch;
     if (const char* e = getenv("EPIPF_SMOOTH_SCRATCH_MB")) budget = (size_t)std::max(1, atoi(e)) << 20;
+    // days per launch of the fixed-lag pass (a workgroup each, with its own global rows): all T, or what the budget holds
+    // beside one chain's histogram, at least one
+    int days = T;
+    if (lagged) {
+        if (rb1 > 0 && hb1 + (size_t)T * rb1 > budget)
+            days = (int)std::max<size_t>(1, std::min<size_t>((size_t)T, (budget > hb1 ? budget - hb1 : 0) / rb1));
+        days = std::min(days, kSmoothLagMaxBlocks);
+    }
+    const size_t mb1 = lagged ? (size_t)days * rb1 : rb1;   // one chain's global rows
     // chains per slice: what the budget holds, at least one (one chain's histogram is within kSmoothHistLimit)
     int slice = n;
     if (hb1 + mb1 > 0) slice = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, budget / (hb1 + mb1)));
+    if (lagged) slice = std::min(slice, std::max(1, kSmoothLagMaxBlocks / days));
     HIP_TRY(hipSetDevice(c->device));
     const size_t ob_s = align256((size_t)n * TC * sizeof(unsigned long long));
     const size_t ob_l = align256((size_t)n * T * sizeof(int32_t));
@@ -1105,7 +1121,19 @@ static int smooth_run(epipf_ctx* c, int n, int T, int N, int C, const int32_t* u
         a.mrows = mb1 ? drows : nullptr;
         a.hist = hb1 ? dhist : nullptr;
         if (hb1) HIP_TRY(hipMemsetAsync(dhist, 0, (size_t)k * hb1, c->stream));
-        hipError_t le = launch_smooth(a, c->stream);
+        hipError_t le = hipSuccess;
+        if (lagged) {
+            SmoothLagArgs la{};
+            la.n = k; la.chain0 = c0; la.T = T; la.N = N; la.C = C; la.shift = a.shift; la.lag = lag; la.bins = bins;
+            la.hist_stride = a.hist_stride; la.anc_stride = a.anc_stride; la.hidden = a.hidden; la.ancestry = a.ancestry;
+            la.status = a.status; la.mrows = a.mrows; la.sums = dsums; la.lineages = dlin; la.hist = a.hist;
+            for (int d0 = 0; d0 < T && le == hipSuccess; d0 += days) {
+                la.day0 = d0; la.days = std::min(days, T - d0);
+                le = launch_smooth_lag(la, c->stream);
+            }
+        } else {
+            le = launch_smooth(a, c->stream);
+        }
         if (le != hipSuccess) return fail(EPIPF_EHIP, "smooth launch failed: %s", hipGetErrorString(le));
         if (n_q > 0) {
             SmoothQuantArgs qa{};
@@ -1125,18 +1153,20 @@ static int smooth_run(epipf_ctx* c, int n, int T, int N, int C, const int32_t* u
     return EPIPF_OK;
 }
 
-int epipf_smooth(epipf_ctx* c, int n_chains, int lineage, int kind, const double* q, int n_q, int bins,
-                 int64_t* sums_out, int32_t* quant_out, int32_t* lineages_out) {
+// epipf_smooth / epipf_smooth_lag: the last run's chains, resident on the device.
+static int smooth_resident(epipf_ctx* c, int n_chains, int lineage, int kind, int lag, const double* q, int n_q, int bins,
+                           int64_t* sums_out, int32_t* quant_out, int32_t* lineages_out) {
     if (!c) return fail(EPIPF_EINVAL, "NULL context");
     if (!c->have_run) return fail(EPIPF_ESTATE, "no filter has run on this context");
     if (n_chains < 1 || n_chains > c->last_chains) return fail(EPIPF_EINVAL, "n_chains=%d outside [1, %d]", n_chains, c->last_chains);
-    return smooth_run(c, n_chains, c->last_T, c->N, c->C, nullptr, nullptr, lineage, kind, q, n_q, bins, sums_out,
+    return smooth_run(c, n_chains, c->last_T, c->N, c->C, nullptr, nullptr, lineage, kind, lag, q, n_q, bins, sums_out,
                       quant_out, lineages_out);
 }
 
-int epipf_smooth_history(epipf_ctx* c, int n, int T, int N, int C, const int32_t* hidden, const int32_t* ancestry,
-                         int lineage, int kind, const double* q, int n_q, int bins, int64_t* sums_out,
-                         int32_t* quant_out, int32_t* lineages_out) {
+// epipf_smooth_history / epipf_smooth_lag_history: the caller's host arrays.
+static int smooth_uploaded(epipf_ctx* c, int n, int T, int N, int C, const int32_t* hidden, const int32_t* ancestry,
+                           int lineage, int kind, int lag, const double* q, int n_q, int bins, int64_t* sums_out,
+                           int32_t* quant_out, int32_t* lineages_out) {
     if (!c || !hidden || !ancestry) return fail(EPIPF_EINVAL, "NULL argument");
     if (n < 1 || T < 1 || N < 1 || C < 1) return fail(EPIPF_EINVAL, "n, T, N, C must be >= 1");
     if ((double)n * T * N * C > (double)((size_t)1 << 40)) return fail(EPIPF_EINVAL, "history too large");
@@ -1144,7 +1174,35 @@ int epipf_smooth_history(epipf_ctx* c, int n, int T, int N, int C, const int32_t
         if (hidden[i] < 0) return fail(EPIPF_EINVAL, "counts must be non-negative");
     for (size_t i = 0; i < (size_t)n * T * N; ++i)
         if (ancestry[i] < 0 || ancestry[i] >= N) return fail(EPIPF_EINVAL, "ancestors must lie in [0, N)");
-    return smooth_run(c, n, T, N, C, hidden, ancestry, lineage, kind, q, n_q, bins, sums_out, quant_out, lineages_out);
+    return smooth_run(c, n, T, N, C, hidden, ancestry, lineage, kind, lag, q, n_q, bins, sums_out, quant_out, lineages_out);
+}
+
+int epipf_smooth(epipf_ctx* c, int n_chains, int lineage, int kind, const double* q, int n_q, int bins,
+                 int64_t* sums_out, int32_t* quant_out, int32_t* lineages_out) {
+    return smooth_resident(c, n_chains, lineage, kind, kSmoothNoLag, q, n_q, bins, sums_out, quant_out, lineages_out);
+}
+
+int epipf_smooth_history(epipf_ctx* c, int n, int T, int N, int C, const int32_t* hidden, const int32_t* ancestry,
+                         int lineage, int kind, const double* q, int n_q, int bins, int64_t* sums_out,
+                         int32_t* quant_out, int32_t* lineages_out) {
+    return smooth_uploaded(c, n, T, N, C, hidden, ancestry, lineage, kind, kSmoothNoLag, q, n_q, bins, sums_out, quant_out,
+                           lineages_out);
+}
+
+// The fixed-lag smoother: the same checks, and the lag's.
+int epipf_smooth_lag(epipf_ctx* c, int n_chains, int lineage, int lag, const double* q, int n_q, int bins,
+                     int64_t* sums_out, int32_t* quant_out, int32_t* lineages_out) {
+    if (lag < 0) return fail(EPIPF_EINVAL, "lag=%d must be >= 0", lag);
+    return smooth_resident(c, n_chains, lineage, EPIPF_SMOOTH_SMOOTHING, lag, q, n_q, bins, sums_out, quant_out,
+                           lineages_out);
+}
+
+int epipf_smooth_lag_history(epipf_ctx* c, int n, int T, int N, int C, const int32_t* hidden, const int32_t* ancestry,
+                             int lineage, int lag, const double* q, int n_q, int bins, int64_t* sums_out,
+                             int32_t* quant_out, int32_t* lineages_out) {
+    if (lag < 0) return fail(EPIPF_EINVAL, "lag=%d must be >= 0", lag);
+    return smooth_uploaded(c, n, T, N, C, hidden, ancestry, lineage, EPIPF_SMOOTH_SMOOTHING, lag, q, n_q, bins, sums_out,
+                           quant_out, lineages_out);
 }
 
 // Iterated filtering: M passes of the filter with theta per particle, all enqueued at once.

@@ -267,14 +267,16 @@ class Engine:
                                      ptr(sums), ptr(hist), int(bins), ptr(ev)), "epipf_forecast")
         return out, sums, hist, int(ev[0])
 
-    def smooth(self, n_chains=None, quantiles=(0.05, 0.5, 0.95), lineage="genealogy", kind="smoothing", bins=None):
+    def smooth(self, n_chains=None, quantiles=(0.05, 0.5, 0.95), lineage="genealogy", kind="smoothing", bins=None,
+               lag=None):
         """Daily means, quantiles and surviving-lineage counts of the last run's first n_chains chains, from the history
         resident on the device (epipf_smooth; epipf.smoothing has the definition).  Returns Smoothed with a leading
         chain axis: mean [n, T, C], quantiles [n, Q, T, C] or None, lineages [n, T], sums [n, T, C], zetas None.  Rows
         of chains whose last status was not OK are NaN in mean and 0 elsewhere.  bins defaults to the population total
-        + 1 (every model conserves it)."""
+        + 1 (every model conserves it).  lag=L: the fixed-lag smoother instead (epipf_smooth_lag)."""
         from . import smoothing
         lin, knd, q = smoothing.check_options(lineage, kind, quantiles)
+        lag = smoothing.check_lag(lag, kind)
         n = int(n_chains) if n_chains is not None else self._last_n or 1   # before any run: the library's EPIPF_ESTATE
         if bins is None:
             if self._pop is None:
@@ -285,15 +287,22 @@ class Engine:
         sums = np.zeros((rows, self.T, self.C), dtype=np.int64)
         lineages = np.zeros((rows, self.T), dtype=np.int32)
         quant = np.zeros((rows, nq, self.T, self.C), dtype=np.int32) if nq else None
-        check(self._L.epipf_smooth(self._h, n, lin, knd, ptr(q), nq, int(bins) if nq else 0, ptr(sums), ptr(quant),
-                                   ptr(lineages)), "epipf_smooth")
+        if lag is None:
+            check(self._L.epipf_smooth(self._h, n, lin, knd, ptr(q), nq, int(bins) if nq else 0, ptr(sums), ptr(quant),
+                                       ptr(lineages)), "epipf_smooth")
+        else:
+            check(self._L.epipf_smooth_lag(self._h, n, lin, min(lag, 2**31 - 1), ptr(q), nq, int(bins) if nq else 0,
+                                           ptr(sums), ptr(quant), ptr(lineages)), "epipf_smooth_lag")
         mean = sums / float(self.N)
         mean[self._last_status[:n] != _lib.STATUS_OK] = np.nan
         return smoothing.Smoothed(mean, None if quant is None else quant.astype(np.int64), lineages, sums, None)
 
-    def smooth_history(self, hidden, ancestry, lineage, kind, q, bins):
+    def smooth_history(self, hidden, ancestry, lineage, kind, q, bins, lag=None):
         """epipf_smooth_history on int32 host arrays hidden [n, T, N, C], ancestry [n, T, N] (this engine's model and N
-        are ignored): (sums [n, T, C] int64, quantiles [n, Q, T, C] int32 or None, lineages [n, T] int32)."""
+        are ignored): (sums [n, T, C] int64, quantiles [n, Q, T, C] int32 or None, lineages [n, T] int32).  lag=L (an
+        integer >= 0, with kind EPIPF_SMOOTH_SMOOTHING): epipf_smooth_lag_history."""
+        from . import smoothing
+        lag = smoothing.check_lag(lag, "predictive" if int(kind) == _lib.SMOOTH_PREDICTIVE else "smoothing")
         hidden = np.ascontiguousarray(hidden, dtype=np.int32)
         ancestry = np.ascontiguousarray(ancestry, dtype=np.int32)
         n, T, N, C = hidden.shape
@@ -301,9 +310,14 @@ class Engine:
         sums = np.zeros((n, T, C), dtype=np.int64)
         lineages = np.zeros((n, T), dtype=np.int32)
         quant = np.zeros((n, nq, T, C), dtype=np.int32) if nq else None
-        check(self._L.epipf_smooth_history(self._h, n, T, N, C, ptr(hidden), ptr(ancestry), int(lineage), int(kind),
-                                           ptr(q), nq, int(bins) if nq else 0, ptr(sums), ptr(quant), ptr(lineages)),
-              "epipf_smooth_history")
+        if lag is None:
+            check(self._L.epipf_smooth_history(self._h, n, T, N, C, ptr(hidden), ptr(ancestry), int(lineage), int(kind),
+                                               ptr(q), nq, int(bins) if nq else 0, ptr(sums), ptr(quant),
+                                               ptr(lineages)), "epipf_smooth_history")
+        else:
+            check(self._L.epipf_smooth_lag_history(self._h, n, T, N, C, ptr(hidden), ptr(ancestry), int(lineage),
+                                                   min(lag, 2**31 - 1), ptr(q), nq, int(bins) if nq else 0, ptr(sums),
+                                                   ptr(quant), ptr(lineages)), "epipf_smooth_lag_history")
         return sums, quant, lineages
 
     def resample(self, w, u):
