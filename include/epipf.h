@@ -16,6 +16,8 @@
  *   epipf_simulate_path  the same functions with last_values_only=False (event times + states)
  *   epipf_forecast       tests/pred_tmps.py:55-64  traj_inf per posterior draw (own theta, own start state), batched:
  *                        the continuous path over [0, H] binned to one row per day, with ensemble sums and histograms
+ *   epipf_forecast_summary   no reference counterpart: peak, peak time, extinction time, infections and events of each
+ *                        of epipf_forecast's continuous paths, reduced on the device
  *   epipf_smooth / epipf_smooth_history   no reference counterpart: the smoothing distribution over the observed window
  *                        (daily means, quantiles, surviving lineages) from the resident history, or from a caller's
  *   epipf_smooth_lag / epipf_smooth_lag_history   no reference counterpart: the fixed-lag smoother, each day from the
@@ -190,6 +192,36 @@ int epipf_simulate_path(epipf_ctx* ctx, int n, const int32_t* states_in, const d
 int epipf_forecast(epipf_ctx* ctx, int n_draws, int replicates, int horizon, const double* theta, int d,
                    const int32_t* states, uint64_t key, uint32_t filter_index, uint32_t step, int32_t* rows_out,
                    int64_t* sums_out, uint32_t* hist_out, int bins, int64_t* events_out);
+
+/* Forecast summaries: functionals of the whole continuous path of every trajectory of epipf_forecast.
+ * A call with the same arguments describes the same paths as epipf_forecast, bit for bit (draw i, replicate r, event k:
+ * counter (k, r, step, filter_index + i)), and a draw depends on nothing else in its batch.  With i(t) the infectious
+ * count after the events up to time t (SIR and SEIR: I; the subgroup models: the sum of I_g), per trajectory:
+ *   peak             the maximum of i over the start state and every accepted event
+ *   peak_time        the time of the first accepted event after which i == peak (the clock value epipf_simulate_path
+ *                    reports for it); 0.0 when no event exceeds the start value
+ *   extinction_time  the time of the accepted event after which nobody is infectious (SEIR: nor exposed); 0.0 when the
+ *                    start state is already so; +inf when the path is still active at the horizon
+ *   infections       susceptibles (summed over groups) at the start minus those of the final state
+ *   events           accepted events
+ * peak_out, peak_time_out, extinction_time_out, infections_out, events_out: [n_draws*replicates] each, draw-major, or
+ * all five NULL (nothing per trajectory leaves the device).  Reductions over the trajectories, exact integers:
+ *   totals_out [4]: sum of peak, sum of infections, extinct trajectories, sum of events
+ *   peak_hist_out, infections_hist_out [bins] uint32, or both NULL: trajectories with each value; bins must exceed the
+ *            largest start-state total
+ *   peak_day_out [horizon] uint32: trajectories with min(floor(peak_time), horizon - 1) equal to each day
+ *   extinct_day_out [horizon+1] uint32: extinct trajectories by min(floor(extinction_time), horizon - 1); entry
+ *            [horizon] counts those that are not extinct.  The running sum up to day k is the number of trajectories
+ *            whose epipf_forecast row k has nobody infected, except that an extinction event at exactly
+ *            t = horizon, which no row holds, counts in entry [horizon - 1]
+ *   extinct_per_draw_out [n_draws] uint32, or NULL: extinct trajectories of each draw
+ * Limits as epipf_forecast's; n_draws == 0 returns EPIPF_OK with zeros. */
+int epipf_forecast_summary(epipf_ctx* ctx, int n_draws, int replicates, int horizon, const double* theta, int d,
+                           const int32_t* states, uint64_t key, uint32_t filter_index, uint32_t step,
+                           int32_t* peak_out, double* peak_time_out, double* extinction_time_out,
+                           int32_t* infections_out, int32_t* events_out, int64_t* totals_out,
+                           uint32_t* peak_hist_out, uint32_t* infections_hist_out, int bins, uint32_t* peak_day_out,
+                           uint32_t* extinct_day_out, uint32_t* extinct_per_draw_out);
 
 /* Particle smoother: daily state estimates over the observed window from a filter's whole history
  * h[T][N][C] (hidden), a[T][N] (ancestry), as a backward pass of integer multiplicities.  With shift = `lineage`:

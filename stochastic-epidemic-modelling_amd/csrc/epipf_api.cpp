@@ -1027,6 +1027,133 @@ int epipf_forecast(epipf_ctx* c, int n_draws, int replicates, int horizon, const
     return EPIPF_OK;
 }
 
+// Path functionals of epipf_forecast's trajectories: the same checks, parameter blocks and streams.
+int epipf_forecast_summary(epipf_ctx* c, int n_draws, int replicates, int horizon, const double* theta, int d,
+                           const int32_t* states, uint64_t key, uint32_t filter_index, uint32_t step,
+                           int32_t* peak_out, double* peak_time_out, double* extinction_time_out,
+                           int32_t* infections_out, int32_t* events_out, int64_t* totals_out,
+                           uint32_t* peak_hist_out, uint32_t* infections_hist_out, int bins, uint32_t* peak_day_out,
+                           uint32_t* extinct_day_out, uint32_t* extinct_per_draw_out) {
+    if (!c || !theta || !states || !totals_out || !peak_day_out || !extinct_day_out)
+        return fail(EPIPF_EINVAL, "NULL argument");
+    if (n_draws < 0) return fail(EPIPF_EINVAL, "n_draws < 0");
+    if (replicates < 1) return fail(EPIPF_EINVAL, "replicates must be >= 1");
+    if (horizon < 1) return fail(EPIPF_EINVAL, "horizon must be >= 1");
+    if (d != theta_dim(c->model, c->G)) return fail(EPIPF_EINVAL, "theta needs %d entries", theta_dim(c->model, c->G));
+    if ((int64_t)n_draws * replicates > INT32_MAX)
+        return fail(EPIPF_EINVAL, "n_draws * replicates must be <= %d", INT32_MAX);
+    if (2 * (int64_t)horizon + 1 > INT32_MAX) return fail(EPIPF_EINVAL, "2 * horizon + 1 must be <= %d", INT32_MAX);
+    const int per_path = (peak_out != nullptr) + (peak_time_out != nullptr) + (extinction_time_out != nullptr) +
+                         (infections_out != nullptr) + (events_out != nullptr);
+    if (per_path != 0 && per_path != 5)
+        return fail(EPIPF_EINVAL, "the five per-path outputs must be all NULL or all non-NULL");
+    if ((peak_hist_out != nullptr) != (infections_hist_out != nullptr))
+        return fail(EPIPF_EINVAL, "the two value histograms must be both NULL or both non-NULL");
+    const bool hist = peak_hist_out != nullptr;
+    const int C = c->C;
+    for (size_t i = 0; i < (size_t)n_draws * d; ++i)
+        if (!(theta[i] >= 0.0 && theta[i] < INFINITY))
+            return fail(EPIPF_EINVAL, "theta[%zu][%zu] must be finite and >= 0", i / d, i % d);
+    int64_t largest = 0;
+    for (int i = 0; i < n_draws; ++i) {
+        int64_t total = 0;
+        for (int k = 0; k < C; ++k) {
+            if (states[(size_t)i * C + k] < 0) return fail(EPIPF_EINVAL, "states must be non-negative");
+            total += states[(size_t)i * C + k];
+        }
+        largest = std::max(largest, total);
+    }
+    // the peak and the infections never exceed a draw's total, which every model conserves: int32, and the histograms' range
+    if (largest > INT32_MAX) return fail(EPIPF_EINVAL, "a draw's state total must be <= %d", INT32_MAX);
+    if (hist && (int64_t)bins <= largest)
+        return fail(EPIPF_EINVAL, "bins must be > %lld, the largest state total", (long long)largest);
+    const size_t H = (size_t)horizon;
+    for (int i = 0; i < 4; ++i) totals_out[i] = 0;
+    if (n_draws == 0) {
+        memset(peak_day_out, 0, sizeof(uint32_t) * H);
+        memset(extinct_day_out, 0, sizeof(uint32_t) * (H + 1));
+        if (hist) {
+            memset(peak_hist_out, 0, sizeof(uint32_t) * (size_t)bins);
+            memset(infections_hist_out, 0, sizeof(uint32_t) * (size_t)bins);
+        }
+        return EPIPF_OK;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const bool wide = c->G > kMaxLaneG;
+    const int n = n_draws * replicates;
+    const size_t pb = align256(cp_slots(c->G, (size_t)n_draws) * sizeof(ChainParam));
+    const size_t sb = align256((size_t)n_draws * C * sizeof(int32_t));
+    // the reductions, zeroed together: totals [4] u64, then uint32 peak_day [H], extinct_day [H + 1],
+    // extinct_per_draw [D], peak_hist [bins], infections_hist [bins]
+    const size_t nb = hist ? (size_t)bins : 0;
+    const size_t n32 = 2 * H + 1 + (size_t)n_draws + 2 * nb;
+    const size_t ub = align256(4 * sizeof(unsigned long long) + n32 * sizeof(uint32_t));
+    const size_t fb = per_path ? align256((size_t)n * sizeof(double)) : 0;     // per path: two f64, then three int32
+    const size_t ib = per_path ? align256((size_t)n * sizeof(int32_t)) : 0;
+    if (ensure_scratch(c, pb + sb + ub + 2 * fb + 3 * ib)) return EPIPF_ENOMEM;
+    char* base = (char*)c->scratch;
+    ChainParam* dcp = (ChainParam*)base;
+    int32_t* din = (int32_t*)(base + pb);
+    unsigned long long* dtot = (unsigned long long*)(base + pb + sb);
+    uint32_t* dpday = (uint32_t*)(dtot + 4);
+    uint32_t* deday = dpday + H;
+    uint32_t* ddraw = deday + H + 1;
+    uint32_t* dphist = ddraw + n_draws;
+    uint32_t* dihist = dphist + nb;
+    double* dptime = (double*)(base + pb + sb + ub);
+    double* detime = (double*)((char*)dptime + fb);
+    int32_t* dpeak = (int32_t*)((char*)detime + fb);
+    int32_t* dinf = (int32_t*)((char*)dpeak + ib);
+    int32_t* dnev = (int32_t*)((char*)dinf + ib);
+    // draw i's parameters; its stream is the single-theta calls' at filter index filter_index + i (wrapping)
+    std::vector<ChainParam> hcp(cp_slots(c->G, (size_t)n_draws));
+    memset(hcp.data(), 0, hcp.size() * sizeof(ChainParam));
+    WideParam* hw = wide ? const_cast<WideParam*>(wide_param(hcp.data(), n_draws, 0)) : nullptr;
+    for (int i = 0; i < n_draws; ++i) {
+        ChainParam& q = hcp[i];
+        for (int k = 0; k < d; ++k) set_theta(q, wide ? hw + i : nullptr, k, theta[(size_t)i * d + k]);
+        q.k0 = (uint32_t)key; q.k1 = (uint32_t)(key >> 32); q.f = filter_index + (uint32_t)i;
+        q.clock_slack = 1.f;
+        q.band_slack = 1.f;
+    }
+    HIP_TRY(hipMemcpyAsync(dcp, hcp.data(), hcp.size() * sizeof(ChainParam), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(din, states, sizeof(int32_t) * (size_t)n_draws * C, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(dtot, 0, ub, c->stream));
+    long long lds_limit = -1;                            // bytes; lowers kForecastSummaryLdsDays (for tests)
+    if (const char* e = getenv("EPIPF_FORECAST_SUMMARY_LDS")) lds_limit = std::max(0ll, atoll(e));
+    ForecastSummaryArgs a{};
+    a.logtab = c->logtab; a.n = n; a.D = n_draws; a.R = replicates; a.H = horizon; a.bins = bins;
+    a.lds_days = forecast_summary_lds_days(horizon, lds_limit) ? 1 : 0;
+    a.step = step; a.cp = dcp; a.in = din;
+    if (per_path) { a.peak = dpeak; a.peak_time = dptime; a.extinction_time = detime; a.infections = dinf; a.events = dnev; }
+    a.totals = dtot; a.peak_day = dpday; a.extinct_day = deday;
+    if (hist) { a.peak_hist = dphist; a.infections_hist = dihist; }
+    a.extinct_per_draw = extinct_per_draw_out ? ddraw : nullptr;
+    hipError_t le = launch_forecast_summary(a, c->model, c->G, c->stream);
+    if (le != hipSuccess) return fail(EPIPF_EHIP, "forecast summary launch failed: %s", hipGetErrorString(le));
+    unsigned long long ht[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(ht, dtot, sizeof ht, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(peak_day_out, dpday, sizeof(uint32_t) * H, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(extinct_day_out, deday, sizeof(uint32_t) * (H + 1), hipMemcpyDeviceToHost, c->stream));
+    if (extinct_per_draw_out)
+        HIP_TRY(hipMemcpyAsync(extinct_per_draw_out, ddraw, sizeof(uint32_t) * (size_t)n_draws, hipMemcpyDeviceToHost, c->stream));
+    if (hist) {
+        HIP_TRY(hipMemcpyAsync(peak_hist_out, dphist, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(infections_hist_out, dihist, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (per_path) {
+        HIP_TRY(hipMemcpyAsync(peak_out, dpeak, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(peak_time_out, dptime, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(extinction_time_out, detime, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(infections_out, dinf, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(events_out, dnev, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 4; ++i) totals_out[i] = (int64_t)ht[i];
+    trim_scratch(c);
+    return EPIPF_OK;
+}
+
 // ------------------------------------------------------------------------------- particle smoother
 // One chain's histogram above this is refused (as epipf.forecast refuses its own); the chains of a call share at most
 // kSmoothScratch of histogram and global multiplicity rows, in slices (EPIPF_SMOOTH_SCRATCH_MB overrides, for tests).

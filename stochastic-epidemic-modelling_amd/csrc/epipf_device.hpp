@@ -319,6 +319,7 @@ struct SsaState<kSIR, 1> {                                             // gilles
         nrec = 0;
     }
     __device__ __forceinline__ bool active() const { return I > 0.0; }   // :48
+    __device__ __forceinline__ double infectious() const { return I; }
     // a0 and scale = 1/sum(a) in the reference's order (:38-39, :62)
     __device__ __forceinline__ double rates(const ChainParam& cp, double& a0) const {
         a0 = ((cp.theta[0] * S) * I) / N;                              // beta * s * i / N
@@ -359,6 +360,7 @@ struct SsaState<kSEIR, 1> {                                            // gilles
         N = ((S + E) + I) + R;                                         // :104
     }
     __device__ __forceinline__ bool active() const { return E > 0.0 || I > 0.0; }   // :119
+    __device__ __forceinline__ double infectious() const { return I; }   // not E
     // cumulative a0, a0 + a1 and scale = 1/sum(a), theta = (beta, alpha, gamma) (:92, :107-109, :133)
     __device__ __forceinline__ double rates(const ChainParam& cp, double& a0, double& a01) const {
         a0 = ((cp.theta[0] * S) * I) / N;
@@ -425,6 +427,12 @@ struct SubgroupsState {                                                // gilles
 #pragma unroll
         for (int g = 0; g < G; ++g) infected = infected + I[g];
         return infected > 0.0;
+    }
+    __device__ __forceinline__ double infectious() const {             // exact integers: the order does not matter
+        double infected = 0.0;
+#pragma unroll
+        for (int g = 0; g < G; ++g) infected = infected + I[g];
+        return infected;
     }
     __device__ __forceinline__ bool event(const Block& r, double& t, double tmax, const ChainParam& cp,
                                           const LogTab* __restrict__ tab) {
@@ -555,6 +563,12 @@ struct SubgroupsStateWide {                                            // gilles
 #pragma unroll
         for (int g = 0; g < G; ++g) infected = infected + I[g];
         return infected > 0.0;
+    }
+    __device__ __forceinline__ double infectious() const {             // exact integers: the order does not matter
+        double infected = 0.0;
+#pragma unroll
+        for (int g = 0; g < G; ++g) infected = infected + I[g];
+        return infected;
     }
     __device__ __forceinline__ bool event(const Block& r, double& t, double tmax, const ChainParam& cp,
                                           const LogTab* __restrict__ tab) {

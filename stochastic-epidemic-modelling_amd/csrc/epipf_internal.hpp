@@ -122,6 +122,29 @@ struct ForecastArgs {
     unsigned long long* events;  // [1] accepted events
 };
 
+// path functionals of the same trajectories (epipf_forecast_summary, epipf_forecast_summary.hpp): per-path arrays are
+// lane order, which is [D][R]
+struct ForecastSummaryArgs {
+    const LogTab* logtab;
+    int n, D, R, H;              // lanes D R, draws, replicates per draw, days
+    int bins;                    // bins of each value histogram: values 0..bins-1
+    int lds_days;                // 1: each block counts the two day histograms in LDS first (forecast_summary_lds_days)
+    uint32_t step;
+    const ChainParam* cp;        // [D], then D WideParam blocks for G > kMaxLaneG
+    const int32_t* in;           // [D][C] start state of each draw
+    int32_t* peak;               // [n] each, or all five null
+    double* peak_time;
+    double* extinction_time;
+    int32_t* infections;
+    int32_t* events;
+    unsigned long long* totals;  // [4] sum of peak, sum of infections, extinct paths, sum of events
+    uint32_t* peak_hist;         // [bins] each, or both null
+    uint32_t* infections_hist;
+    uint32_t* peak_day;          // [H]
+    uint32_t* extinct_day;       // [H + 1]; bin H: the paths that are not extinct
+    uint32_t* extinct_per_draw;  // [D], or null
+};
+
 struct ResampleArgs {
     int N, B;
     double cert_k;
@@ -259,6 +282,11 @@ hipError_t launch_forecast_wide(const ForecastArgs& a, int G, hipStream_t s);
 // lane-minor rows [HC][n] -> [n][HC] (HC = H C); hipErrorInvalidValue beyond 65535 x 64 cells per trajectory
 hipError_t launch_forecast_transpose(const int32_t* in, int32_t* out, int n, int HC, hipStream_t s);
 bool forecast_lds_sums(int H, int C);   // the [H][C] block sums fit the launch's dynamic LDS
+// the forecast summary kernel (epipf_forecast_summary.hip; G = 5..8: epipf_forecast_summary_wide.hip)
+hipError_t launch_forecast_summary(const ForecastSummaryArgs& a, int model, int G, hipStream_t s);
+hipError_t launch_forecast_summary_wide(const ForecastSummaryArgs& a, int G, hipStream_t s);
+// the [H] + [H + 1] day histograms fit the block's LDS share; limit >= 0 lowers the bound to that many bytes
+bool forecast_summary_lds_days(int H, long long limit);
 hipError_t launch_abc_trials(const AbcArgs& a, hipStream_t s, hipStream_t s2, hipEvent_t fork, hipEvent_t join);
 size_t abc_sort_temp_bytes(int n);
 hipError_t launch_abc_select(const AbcSelectArgs& a, hipStream_t s);

@@ -28,7 +28,7 @@ EXPORTS = (
     "epipf_build_id", "epipf_max_groups",
     "epipf_abc", "epipf_abc_trials", "epipf_glibc_log", "epipf_clock_log", "epipf_simulate_path",
     "epipf_forecast", "epipf_abc_smc_generation", "epipf_abc_smc_weights", "epipf_smooth", "epipf_smooth_history",
-    "epipf_iterated_filtering_subgroups", "epipf_smooth_lag", "epipf_smooth_lag_history",
+    "epipf_iterated_filtering_subgroups", "epipf_smooth_lag", "epipf_smooth_lag_history", "epipf_forecast_summary",
 )
 # Entry points whose names carry a digit, listed apart: EXPORTS is compared with the header's names as a letters-only
 # pattern finds them (tests/test_abi.py), which stops at the digit.  tests/test_if2_host.py checks these the same way.
@@ -122,6 +122,7 @@ def load():
         "epipf_clock_log": ([ctypes.c_int64, P, P], i32),
         "epipf_simulate_path": ([P, i32, P, P, i32, f64, u64, u32, u32, i32, P, P, P, P], i32),
         "epipf_forecast": ([P, i32, i32, i32, P, i32, P, u64, u32, u32, P, P, P, i32, P], i32),
+        "epipf_forecast_summary": ([P, i32, i32, i32, P, i32, P, u64, u32, u32, P, P, P, P, P, P, P, P, i32, P, P, P], i32),
         "epipf_abc_smc_generation": ([P, P, i32, i32, f64, P, P, P, i32, P, u64, u32, u32, ctypes.c_int64, i32,
                                       P, P, P, P, P, P], i32),
         "epipf_abc_smc_weights": ([P, P, i32, P, P, i32, P, P], i32),

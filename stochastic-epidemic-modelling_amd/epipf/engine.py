@@ -267,6 +267,36 @@ class Engine:
                                      ptr(sums), ptr(hist), int(bins), ptr(ev)), "epipf_forecast")
         return out, sums, hist, int(ev[0])
 
+    def forecast_summary(self, thetas, states, horizon, replicates=1, key=0, filter_index=0, step=0, per_path=False,
+                         bins=0):
+        """epipf_forecast_summary: path functionals of forecast()'s trajectories (same arguments, same paths).  Returns
+        a dict of the raw arrays: totals [4] int64 (sum of peak, sum of infections, extinct paths, sum of events),
+        peak_day [H], extinct_day [H + 1], extinct_per_draw [D] uint32, peak_hist / infections_hist [bins] uint32 (None
+        when bins == 0), and paths: None, or (peak int32, peak_time, extinction_time float64, infections, events int32),
+        each [D, R]."""
+        thetas = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64))
+        states = np.ascontiguousarray(np.asarray(states, dtype=np.int32).reshape(-1, self.C))
+        D, H, R = states.shape[0], int(horizon), int(replicates)
+        if thetas.ndim != 2 or thetas.shape[0] != D:
+            raise ValueError(f"thetas must be [{D}, d], one row per start state")
+        paths = None
+        if per_path:
+            paths = tuple(np.zeros((D, max(R, 0)), dtype=t) for t in (np.int32, np.float64, np.float64, np.int32, np.int32))
+        pp = paths or (None,) * 5
+        totals = np.zeros(4, dtype=np.int64)
+        peak_day = np.zeros(max(H, 0), dtype=np.uint32)
+        extinct_day = np.zeros(max(H, 0) + 1, dtype=np.uint32)
+        per_draw = np.zeros(D, dtype=np.uint32)
+        peak_hist = np.zeros(int(bins), dtype=np.uint32) if bins else None
+        inf_hist = np.zeros(int(bins), dtype=np.uint32) if bins else None
+        check(self._L.epipf_forecast_summary(self._h, D, R, H, ptr(thetas), thetas.shape[1], ptr(states),
+                                             int(key) & (2**64 - 1), int(filter_index) & 0xFFFFFFFF, int(step),
+                                             ptr(pp[0]), ptr(pp[1]), ptr(pp[2]), ptr(pp[3]), ptr(pp[4]), ptr(totals),
+                                             ptr(peak_hist), ptr(inf_hist), int(bins), ptr(peak_day), ptr(extinct_day),
+                                             ptr(per_draw)), "epipf_forecast_summary")
+        return dict(totals=totals, peak_day=peak_day, extinct_day=extinct_day, extinct_per_draw=per_draw,
+                    peak_hist=peak_hist, infections_hist=inf_hist, paths=paths)
+
     def smooth(self, n_chains=None, quantiles=(0.05, 0.5, 0.95), lineage="genealogy", kind="smoothing", bins=None,
                lag=None):
         """Daily means, quantiles and surviving-lineage counts of the last run's first n_chains chains, from the history
