@@ -33,6 +33,9 @@
  *   epipf_if2            no reference counterpart (its PMCMC scripts start from hand-tuned runs): iterated filtering, a
  *                        maximum-likelihood search by filters whose particles each carry and jitter their own theta
  *   epipf_iterated_filtering_subgroups   the same search for the subgroup models at G = 2..4 (theta = beta[G][G], gamma)
+ *   epipf_walk_filter / epipf_walk_history / epipf_walk_smooth / epipf_walk_smooth_history   no reference counterpart:
+ *                        time-varying rates -- the filter of "theta follows a reflected random walk" with every day's
+ *                        parameters kept, and smoothed daily beta, gamma and R_t as mean and quantiles
  *
  * The host wrapper (stochastic-epidemic-modelling_amd/epipf/) binds these with ctypes and keeps
  * the reference's Python signatures.  Conventions:
@@ -356,6 +359,50 @@ int epipf_iterated_filtering_subgroups(epipf_ctx* ctx, int n_searches, int itera
                                        const double* half_widths, int obs_model, const double* probs,
                                        const uint64_t* keys, const uint32_t* filter_index0, double* log_zetas_out,
                                        double* mean_out, int32_t* iterations_done_out, int32_t* status_out);
+
+/* Time-varying rates for the SIR (d = 2) and SEIR (d = 3) models.
+ * epipf_walk_filter is one pass of epipf_if2 (iterations = 1, m = 0: the same perturb, Philox domain 7 << 24, counters,
+ * weights, resampling, SSA and degeneracy rule) with a half-width vector per chain, half_widths [n_chains*d] (finite,
+ * >= 0; an entry of 0 keeps that component bit for bit), in which every day's parameters theta_p are kept on the device
+ * (theta_hist f64 [chain][T][d][N], allocated on first use, regrown when a call needs more, freed by epipf_destroy;
+ * EPIPF_ENOMEM names the bytes asked for).  It is the bootstrap filter of the model "theta follows a reflected uniform
+ * random walk": log_zetas_out[s][T-1] estimates that model's likelihood at chain s's step widths.
+ *   swarm_in [n_chains*N*d] (finite, >= 0): the sample theta_0 is jittered from;  probs, keys, filter_index [n_chains]
+ *   log_zetas_out [n_chains*T];  status_out [n_chains]
+ * hidden, ancestry, status and log_zeta are the context's: epipf_copy_history, epipf_path_sample and epipf_smooth see the
+ * pass afterwards.  A chain that degenerates at step p keeps its rows < p; its log_zetas from p on are -inf.
+ * EPIPF_EINVAL on a subgroup context. */
+int epipf_walk_filter(epipf_ctx* ctx, int n_chains, const double* swarm_in, int d, const double* half_widths,
+                      int obs_model, const double* probs, const uint64_t* keys, const uint32_t* filter_index,
+                      double* log_zetas_out, int32_t* status_out);
+
+/* theta_out [n_chains*T*N*d]: the parameter history of the last epipf_walk_filter (NaN in a degenerate chain's rows from
+ * its dying step on).  EPIPF_ESTATE before any epipf_walk_filter, and after another run (epipf_run, epipf_if2, ...) has
+ * overwritten the context's history. */
+int epipf_walk_history(epipf_ctx* ctx, int n_chains, double* theta_out);
+
+/* The smoothed parameters.  Particle i of day p has V = d + 1 quantities: v_c = theta_p[i][c] + 0.0 for c < d, and
+ *   v_d = R = (theta_p[i][0] * (double)S_p[i]) / (theta_p[i][d-1] * P) + 0.0, +inf where the denominator is 0.0
+ * (S = compartment 0, P = the population total; no contraction).  With m[p][i] the multiplicities of epipf_smooth_lag at
+ * `lag` (lag < 0 or lag >= T-1: the full smoother; lag 0: the particle cloud) under `lineage`:
+ *   lineages_out [n*T]        #{i : m[p][i] > 0}
+ *   mean_out [n*T*V]          sum_i m[p][i] v_k[i] / N over the i with m > 0, summed in a fixed order (no floating-point
+ *                             atomics: the same bits on every run; within (N + 1) 2^-53 relative of the exact value)
+ *   quant_out [n*n_q*T*V]     the smallest v_k[i] whose cumulative multiplicity reaches max(ceil(q N), 1): numpy's
+ *                             inverted_cdf quantile of the values repeated m times, an element of the input, bit for bit
+ *                             (NULL with n_q = 0)
+ * Chains whose status is not EPIPF_STATUS_OK are not walked: their rows are zeros.  EPIPF_ESTATE as epipf_walk_history. */
+int epipf_walk_smooth(epipf_ctx* ctx, int n_chains, int lineage, int lag, const double* q, int n_q, double* mean_out,
+                      double* quant_out, int32_t* lineages_out);
+
+/* The same reduction on host arrays hidden [n*T*N*C] (only compartment 0 is read), ancestry [n*T*N] and theta
+ * [n*T*N*d], 1 <= d <= 3, with P = population_total (finite, > 0); the context's own shape is ignored, as in
+ * epipf_smooth_history.  EPIPF_EINVAL, naming the first offending index, for a negative, NaN or infinite theta entry, a
+ * negative hidden entry or an ancestor outside [0, N). */
+int epipf_walk_smooth_history(epipf_ctx* ctx, int n, int T, int N, int C, int d, const int32_t* hidden,
+                              const int32_t* ancestry, const double* theta, double population_total, int lineage,
+                              int lag, const double* q, int n_q, double* mean_out, double* quant_out,
+                              int32_t* lineages_out);
 
 /* The device's restatement of glibc's log (the reference's math.log / numpy legacy exponential),
  * evaluated on the host CPU with the same code and table: out[i] = log(x[i]) bit for bit for normal x[i] > 0.

@@ -25,6 +25,7 @@
 #include "epipf_internal.hpp"
 #include "epipf_smooth.hpp"
 #include "epipf_smooth_lag.hpp"
+#include "epipf_walk.hpp"
 
 using namespace epipf;
 
@@ -136,6 +137,11 @@ struct epipf_ctx {
     uint64_t y_hash = 0;     // FNV-1a of the observations (epipf_set_observations): part of the path choice's key
     double split_p = -1.0;   // probs of the cached hi/lo split of log p, log1p(-p) (chains usually share probs)
     double split[4] = {0, 0, 0, 0};
+    // the random-walk filter's parameter history (epipf_walk_filter): theta_hist [chains][T][d][N],
+    // allocated on first use and regrown when a call needs more; walk_valid while it belongs to the context's history
+    double* walk_theta = nullptr;
+    size_t walk_bytes = 0;
+    bool walk_valid = false;
 };
 
 // Lanes per particle for a run of n_chains filters.  The one-lane kernel needs ~20k waves per launch to fill the
@@ -337,7 +343,7 @@ static void free_ctx(epipf_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void* dev[] = {c->hidden, c->ancestry, c->res, c->chosen, c->traj, c->wraw, c->wloc, c->bsum,
-                   c->Y, c->lf, c->cp, c->logtab, c->scratch, c->abc};
+                   c->Y, c->lf, c->cp, c->logtab, c->scratch, c->abc, c->walk_theta};
     for (void* p : dev)
         if (p) (void)hipFree(p);
     void* host[] = {c->h_cp, c->h_res, c->h_traj};
@@ -614,6 +620,7 @@ static int run_impl(epipf_ctx* c, int n_chains, const double* theta, int d, int 
         n_active += on;
     }
     HIP_TRY(hipSetDevice(c->device));
+    c->walk_valid = false;                               // the history is this run's from here on
     HIP_TRY(hipMemcpyAsync(c->cp, c->h_cp, sizeof(ChainParam) * n_chains, hipMemcpyHostToDevice, c->stream));
     if (c->G > kMaxLaneG)   // the chains' WideParam blocks, behind the ChainParam array on both sides
         HIP_TRY(hipMemcpyAsync(const_cast<WideParam*>(wide_param(c->cp, c->max_chains, 0)), wide_param(c->h_cp, c->max_chains, 0),
@@ -1360,6 +1367,7 @@ static int if2_impl(epipf_ctx* c, bool subgroups, int n_searches, int iterations
         q.chosen = -1;
     }
     HIP_TRY(hipSetDevice(c->device));
+    c->walk_valid = false;                               // the history is this call's from here on
     // scratch: swarm [2][max_chains][d][N] | start [max_chains][d][N] | log_zeta [M][max_chains][T] | mean [S][M][d] | done [S]
     const size_t comp = (size_t)d * N, mc = (size_t)c->max_chains;
     const size_t b_swarm = align256(sizeof(double) * 2 * mc * comp), b_start = align256(sizeof(double) * mc * comp);
@@ -1489,6 +1497,285 @@ int epipf_iterated_filtering_subgroups(epipf_ctx* c, int n_searches, int iterati
                     kMaxLaneG, c->G);
     return if2_impl(c, true, n_searches, iterations, swarm_inout, d, half_widths, obs_model, probs, keys, filter_index0,
                     log_zetas_out, mean_out, iterations_done_out, status_out);
+}
+
+// ------------------------------------------------------------------------ time-varying rates
+// The random-walk filter: epipf_if2's pass at one iteration with a half-width vector per chain, every day's swarm kept
+// in theta_hist.  hidden, ancestry, status and log_zeta are the context's own, so epipf_copy_history, epipf_path_sample
+// and epipf_smooth see the pass afterwards.
+int epipf_walk_filter(epipf_ctx* c, int n_chains, const double* swarm_in, int d, const double* half_widths, int obs_model,
+                      const double* probs, const uint64_t* keys, const uint32_t* filter_index, double* log_zetas_out,
+                      int32_t* status_out) {
+    if (!c || !swarm_in || !half_widths || !probs || !keys || !filter_index || !log_zetas_out || !status_out)
+        return fail(EPIPF_EINVAL, "NULL argument");
+    if (c->model != EPIPF_SIR && c->model != EPIPF_SEIR)
+        return fail(EPIPF_EINVAL, "the random-walk filter covers the SIR and SEIR models; the subgroup models are out of its scope");
+    if (!c->have_Y) return fail(EPIPF_ESTATE, "epipf_set_observations was not called");
+    if (!c->have_pop) return fail(EPIPF_ESTATE, "epipf_set_population was not called");
+    const int S = n_chains, N = c->N, T = c->T;
+    if (d != theta_dim(c->model, c->G)) return fail(EPIPF_EINVAL, "theta has %d entries per particle, model needs %d", d, theta_dim(c->model, c->G));
+    if (S < 1 || S > c->max_chains) return fail(EPIPF_EINVAL, "n_chains=%d outside [1, max_chains=%d]", S, c->max_chains);
+    if (obs_model != EPIPF_OBS_BINOMIAL && obs_model != EPIPF_OBS_NORMAL) return fail(EPIPF_EINVAL, "bad obs_model %d", obs_model);
+    for (size_t i = 0; i < (size_t)S * d; ++i)
+        if (!(half_widths[i] >= 0.0 && half_widths[i] < INFINITY))
+            return fail(EPIPF_EINVAL, "half_widths[%zu][%zu]=%g: half-widths must be finite and >= 0", i / d, i % d, half_widths[i]);
+    for (size_t i = 0; i < (size_t)S * N * d; ++i)
+        if (!(swarm_in[i] >= 0.0 && swarm_in[i] < INFINITY))
+            return fail(EPIPF_EINVAL, "swarm[%zu][%zu][%zu]=%g: parameters must be finite and >= 0", i / ((size_t)N * d),
+                        i / d % N, i % d, swarm_in[i]);
+    for (int s = 0; s < S; ++s) {
+        ChainParam& q = c->h_cp[s];
+        memset(&q, 0, sizeof q);                         // theta is the particles' own
+        set_chain_stream(c, q, probs[s], keys[s], filter_index[s]);
+        q.chosen = -1;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    c->walk_valid = false;
+    const size_t comp = (size_t)d * N, stride = (size_t)T * comp;
+    const size_t need = sizeof(double) * (size_t)S * stride;
+    if (need > c->walk_bytes) {
+        if (c->walk_theta) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->walk_theta); }
+        c->walk_theta = nullptr;
+        c->walk_bytes = 0;
+        if (hipMalloc((void**)&c->walk_theta, need) != hipSuccess) {
+            c->walk_theta = nullptr;
+            (void)hipGetLastError();
+            return fail(EPIPF_ENOMEM, "the parameter history needs %zu bytes (%d chains x %d days x %d x %d doubles): hipMalloc failed",
+                        need, S, T, d, N);
+        }
+        c->walk_bytes = need;
+    }
+    // scratch: start [S][d][N] | hw [S][d]
+    const size_t b_start = align256(sizeof(double) * (size_t)S * comp), b_hw = align256(sizeof(double) * (size_t)S * d);
+    if (ensure_scratch(c, b_start + b_hw)) return EPIPF_ENOMEM;
+    double* d_start = (double*)c->scratch;
+    double* d_hw = (double*)((char*)c->scratch + b_start);
+    std::vector<double> soa((size_t)S * comp);            // [S][N][d] -> [S][d][N]
+    for (int s = 0; s < S; ++s)
+        for (int j = 0; j < N; ++j)
+            for (int k = 0; k < d; ++k) soa[((size_t)s * d + k) * N + j] = swarm_in[((size_t)s * N + j) * d + k];
+    HIP_TRY(hipMemcpyAsync(c->cp, c->h_cp, sizeof(ChainParam) * S, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_start, soa.data(), sizeof(double) * soa.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_hw, half_widths, sizeof(double) * (size_t)S * d, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->log_zeta, 0xFF, sizeof(double) * (size_t)S * T, c->stream));   // rows never written read as NaN
+    const size_t b_counters = sizeof(unsigned long long) * (size_t)kCounterSlots * kCounterStride;
+    HIP_TRY(hipMemsetAsync(c->counters, 0, b_counters, c->stream));
+
+    WalkArgs a{};
+    StepArgs& s = a.s;
+    s.N = N; s.T = T; s.max_chains = c->max_chains; s.wg = 64; s.B = (N + 63) / 64; s.lanes = 1; s.lane_events = 1;
+    s.resample_mode = EPIPF_RESAMPLE_MULTINOMIAL; s.lf_max = c->lf_max;
+    s.count_events = c->profiling >= EPIPF_PROFILE_COUNTERS ? 1 : 0;
+    s.hist_stride = c->hist_stride; s.anc_stride = c->anc_stride; s.wstride = c->wstride; s.bstride = c->bstride;
+    s.seg = prefix_segment(s.B);
+    s.nseg = (s.B + s.seg - 1) / s.seg;
+    s.cert_k = cert_k(N, s.B, s.seg, 64);
+    s.Y = c->Y; s.lf = c->lf; s.logtab = c->logtab; s.cp = c->cp; s.hidden = c->hidden; s.ancestry = c->ancestry;
+    s.wraw = c->wraw; s.wloc = c->wloc; s.bsum = c->bsum; s.log_zeta = c->log_zeta; s.status = c->status; s.counters = c->counters;
+    s.xcd_map = c->xcd_map;
+    for (int g = 0; g < kMaxLaneG; ++g) { s.npop[g] = c->npop[g]; s.mu[g] = c->mu[g]; s.emu[g] = c->emu[g]; s.kmax[g] = c->kmax[g]; }
+    a.d = d; a.hw = d_hw; a.start = d_start; a.hist = c->walk_theta; a.chain_stride = stride;
+
+    FilterStreams fs{};
+    fs.n = std::min(c->n_streams, S);
+    if (!ensure_streams(c, fs.n)) return fail(EPIPF_EHIP, "auxiliary stream creation failed");
+    fs.s[0] = c->stream;
+    if (fs.n > 1) HIP_TRY(hipEventRecord(c->fork, c->stream));    // the groups' inputs are on c->stream
+    for (int g = 1; g < fs.n; ++g) {
+        fs.s[g] = c->aux[g];
+        fs.join[g] = c->join[g];
+        HIP_TRY(hipStreamWaitEvent(c->aux[g], c->fork, 0));
+    }
+    c->last_groups = fs.n;
+    const hipError_t le = launch_walk(a, c->model, obs_model, S, fs);
+    if (le != hipSuccess) return fail(EPIPF_EHIP, "kernel launch failed: %s", hipGetErrorString(le));
+    HIP_TRY(hipMemcpyAsync(log_zetas_out, c->log_zeta, sizeof(double) * (size_t)S * T, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(status_out, c->status, sizeof(int32_t) * S, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_counters, c->counters, b_counters, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemsetAsync(c->counters, 0, b_counters, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    unsigned long long tot[kNumCounters] = {};
+    for (int sl = 0; sl < kCounterSlots; ++sl)
+        for (int k = 0; k < kNumCounters; ++k) tot[k] += c->h_counters[(size_t)sl * kCounterStride + k];
+    c->stats.resample_fallbacks = (int64_t)tot[1];
+    if (s.count_events) {
+        c->stats.events = (int64_t)tot[0];
+        c->stats.lane_iterations = (int64_t)tot[2];
+        c->stats.wave_lane_slots = (int64_t)tot[3];
+        c->stats.ssa_exact_lanes = (int64_t)tot[4];
+        c->stats.ssa_exact_waves = (int64_t)tot[5];
+    }
+    // a chain that died at step p wrote -inf there and nothing after: its later days are -inf as well
+    for (int q = 0; q < S; ++q)
+        if (status_out[q] == EPIPF_STATUS_DEGENERATE)
+            for (int p = 0; p < T; ++p)
+                if (std::isnan(log_zetas_out[(size_t)q * T + p])) log_zetas_out[(size_t)q * T + p] = -INFINITY;
+    c->stats.particle_steps += (int64_t)S * N * T;
+    c->stats.filters += S;
+    c->stats.last_lanes = 1;
+    c->stats.last_lane_events = 1;
+    c->stats.last_fused = 0;
+    c->last_chains = S;
+    c->last_T = T;
+    c->have_run = true;
+    c->walk_valid = true;
+    trim_scratch(c);
+    return EPIPF_OK;
+}
+
+static int walk_state(const epipf_ctx* c, int n_chains) {
+    if (!c->walk_valid)
+        return fail(EPIPF_ESTATE, c->have_run ? "the context's history is no longer a random-walk filter's: another run overwrote it"
+                                              : "no random-walk filter has run on this context");
+    if (n_chains < 1 || n_chains > c->last_chains) return fail(EPIPF_EINVAL, "n_chains=%d outside [1, %d]", n_chains, c->last_chains);
+    return 0;
+}
+
+// theta_out [n][T][N][d]; the rows of a degenerate chain from its dying step on are NaN (the device never wrote them).
+int epipf_walk_history(epipf_ctx* c, int n_chains, double* theta_out) {
+    if (!c || !theta_out) return fail(EPIPF_EINVAL, "NULL argument");
+    if (int rc = walk_state(c, n_chains)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const int T = c->last_T, N = c->N, d = theta_dim(c->model, c->G);
+    const size_t stride = (size_t)T * d * N;
+    std::vector<double> soa((size_t)n_chains * stride), lz((size_t)n_chains * T);
+    std::vector<int32_t> st((size_t)n_chains);
+    HIP_TRY(hipMemcpyAsync(soa.data(), c->walk_theta, sizeof(double) * soa.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(lz.data(), c->log_zeta, sizeof(double) * lz.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(st.data(), c->status, sizeof(int32_t) * st.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int s = 0; s < n_chains; ++s) {
+        int alive = T;                                   // days whose rows were written
+        if (st[s] != EPIPF_STATUS_OK)
+            for (alive = 0; alive < T && lz[(size_t)s * T + alive] > -INFINITY; ++alive) {}
+        for (int p = 0; p < T; ++p)
+            for (int j = 0; j < N; ++j)
+                for (int k = 0; k < d; ++k)
+                    theta_out[(((size_t)s * T + p) * N + j) * d + k] =
+                        p < alive ? soa[(size_t)s * stride + ((size_t)p * d + k) * N + j] : NAN;
+    }
+    return EPIPF_OK;
+}
+
+// The reduction over n chains: the context's own history and theta_hist (up_hidden == NULL) or the caller's arrays,
+// uploaded to scratch with theta already [n][T][d][N].  One workgroup per (chain, day); chains and days are sliced so
+// that the global multiplicity rows of a launch (N > kSmoothLdsMaxN) stay within the smoother's scratch budget.
+static int walk_smooth_run(epipf_ctx* c, int n, int T, int N, int C, int d, double pop, const int32_t* up_hidden,
+                           const int32_t* up_ancestry, const double* up_theta, int lineage, int lag, const double* q, int n_q,
+                           double* mean_out, double* quant_out, int32_t* lineages_out) {
+    if (!mean_out || !lineages_out) return fail(EPIPF_EINVAL, "NULL argument");
+    if (lineage != EPIPF_LINEAGE_REFERENCE && lineage != EPIPF_LINEAGE_GENEALOGY)
+        return fail(EPIPF_EINVAL, "unknown lineage %d", lineage);
+    if (n_q < 0 || (n_q > 0 && !q)) return fail(EPIPF_EINVAL, "n_q=%d needs q", n_q);
+    if (n_q > 0 && !quant_out) return fail(EPIPF_EINVAL, "quantiles need quant_out");
+    for (int i = 0; i < n_q; ++i)
+        if (!(q[i] >= 0.0 && q[i] <= 1.0)) return fail(EPIPF_EINVAL, "q[%d] must lie in [0, 1]", i);
+    if (N > kSmoothMaxN) return fail(EPIPF_EINVAL, "at most %d particles, got %d", kSmoothMaxN, N);
+    if (lag < 0 || lag > T - 1) lag = T - 1;              // "full"
+    const int V = d + 1;
+    bool lds_rows = N <= kSmoothLdsMaxN;
+    if (const char* e = getenv("EPIPF_SMOOTH_LDS")) lds_rows = lds_rows && atoi(e) != 0;
+    const size_t rb1 = lds_rows ? 0 : 2 * sizeof(uint32_t) * (size_t)N;   // one workgroup's global rows
+    size_t budget = kSmoothScratch;
+    if (const char* e = getenv("EPIPF_SMOOTH_SCRATCH_MB")) budget = (size_t)std::max(1, atoi(e)) << 20;
+    int days = T;
+    if (rb1 > 0 && (size_t)T * rb1 > budget) days = (int)std::max<size_t>(1, std::min<size_t>((size_t)T, budget / rb1));
+    days = std::min(days, kSmoothLagMaxBlocks);
+    int slice = n;
+    if (rb1 > 0) slice = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, budget / ((size_t)days * rb1)));
+    slice = std::min(slice, std::max(1, kSmoothLagMaxBlocks / days));
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t ob_m = align256(sizeof(double) * (size_t)n * T * V);
+    const size_t ob_q = n_q > 0 ? align256(sizeof(double) * (size_t)n * n_q * T * V) : 0;
+    const size_t ob_l = align256(sizeof(int32_t) * (size_t)n * T);
+    const size_t ob_r = n_q > 0 ? align256(sizeof(uint32_t) * (size_t)n_q) : 0;
+    const size_t sb_m = align256((size_t)slice * days * rb1);
+    const size_t ub_h = up_hidden ? align256(sizeof(int32_t) * (size_t)n * T * N * C) : 0;
+    const size_t ub_a = up_hidden ? align256(sizeof(int32_t) * (size_t)n * T * N) : 0;
+    const size_t ub_t = up_hidden ? align256(sizeof(double) * (size_t)n * T * N * d) : 0;
+    if (ensure_scratch(c, ob_m + ob_q + ob_l + ob_r + sb_m + ub_h + ub_a + ub_t)) return EPIPF_ENOMEM;
+    char* p = (char*)c->scratch;
+    double* dmean = (double*)p; p += ob_m;
+    double* dquant = (double*)p; p += ob_q;
+    int32_t* dlin = (int32_t*)p; p += ob_l;
+    uint32_t* dranks = (uint32_t*)p; p += ob_r;
+    uint32_t* drows = (uint32_t*)p; p += sb_m;
+    int32_t* dhid = (int32_t*)p; p += ub_h;
+    int32_t* danc = (int32_t*)p; p += ub_a;
+    double* dth = (double*)p;
+    HIP_TRY(hipMemsetAsync(dmean, 0, ob_m + ob_q + ob_l, c->stream));
+    std::vector<uint32_t> ranks((size_t)n_q);
+    for (int i = 0; i < n_q; ++i) ranks[i] = (uint32_t)std::max(std::ceil(q[i] * (double)N), 1.0);   // inverted_cdf, q N in float64
+    if (n_q > 0) HIP_TRY(hipMemcpyAsync(dranks, ranks.data(), sizeof(uint32_t) * n_q, hipMemcpyHostToDevice, c->stream));
+    WalkSmoothArgs a{};
+    a.T = T; a.N = N; a.C = C; a.d = d; a.shift = lineage == EPIPF_LINEAGE_GENEALOGY ? 1 : 0; a.lag = lag; a.n_q = n_q;
+    a.pop = pop; a.ranks = n_q > 0 ? dranks : nullptr; a.mean = dmean; a.quant = dquant; a.lineages = dlin;
+    if (up_hidden) {
+        HIP_TRY(hipMemcpyAsync(dhid, up_hidden, sizeof(int32_t) * (size_t)n * T * N * C, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(danc, up_ancestry, sizeof(int32_t) * (size_t)n * T * N, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(dth, up_theta, sizeof(double) * (size_t)n * T * N * d, hipMemcpyHostToDevice, c->stream));
+        a.hidden = dhid; a.ancestry = danc; a.theta = dth; a.status = nullptr;
+        a.hist_stride = (size_t)T * N * C; a.anc_stride = (size_t)T * N; a.theta_stride = (size_t)T * N * d;
+    } else {
+        a.hidden = c->hidden; a.ancestry = c->ancestry; a.theta = c->walk_theta; a.status = c->status;
+        a.hist_stride = c->hist_stride; a.anc_stride = c->anc_stride; a.theta_stride = (size_t)T * N * d;
+    }
+    for (int c0 = 0; c0 < n; c0 += slice) {
+        a.n = std::min(slice, n - c0);
+        a.chain0 = c0;
+        a.mrows = rb1 ? drows : nullptr;
+        for (int d0 = 0; d0 < T; d0 += days) {
+            a.day0 = d0;
+            a.days = std::min(days, T - d0);
+            const hipError_t le = launch_walk_smooth(a, c->stream);
+            if (le != hipSuccess) return fail(EPIPF_EHIP, "walk smooth launch failed: %s", hipGetErrorString(le));
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(mean_out, dmean, sizeof(double) * (size_t)n * T * V, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(lineages_out, dlin, sizeof(int32_t) * (size_t)n * T, hipMemcpyDeviceToHost, c->stream));
+    if (n_q > 0)
+        HIP_TRY(hipMemcpyAsync(quant_out, dquant, sizeof(double) * (size_t)n * n_q * T * V, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    trim_scratch(c);
+    return EPIPF_OK;
+}
+
+int epipf_walk_smooth(epipf_ctx* c, int n_chains, int lineage, int lag, const double* q, int n_q, double* mean_out,
+                      double* quant_out, int32_t* lineages_out) {
+    if (!c) return fail(EPIPF_EINVAL, "NULL context");
+    if (int rc = walk_state(c, n_chains)) return rc;
+    return walk_smooth_run(c, n_chains, c->last_T, c->N, c->C, theta_dim(c->model, c->G), c->npop[0], nullptr, nullptr,
+                           nullptr, lineage, lag, q, n_q, mean_out, quant_out, lineages_out);
+}
+
+int epipf_walk_smooth_history(epipf_ctx* c, int n, int T, int N, int C, int d, const int32_t* hidden,
+                              const int32_t* ancestry, const double* theta, double population_total, int lineage, int lag,
+                              const double* q, int n_q, double* mean_out, double* quant_out, int32_t* lineages_out) {
+    if (!c || !hidden || !ancestry || !theta) return fail(EPIPF_EINVAL, "NULL argument");
+    if (n < 1 || T < 1 || N < 1 || C < 1) return fail(EPIPF_EINVAL, "n, T, N, C must be >= 1");
+    if (d < 1 || d > kIf2MaxD) return fail(EPIPF_EINVAL, "d=%d outside [1, %d]", d, kIf2MaxD);
+    if (!(population_total > 0.0 && population_total < INFINITY))
+        return fail(EPIPF_EINVAL, "population_total=%g must be finite and > 0", population_total);
+    if ((double)n * T * N * std::max(C, 2 * d) > (double)((size_t)1 << 40)) return fail(EPIPF_EINVAL, "history too large");
+    const size_t TN = (size_t)T * N;
+    for (size_t i = 0; i < (size_t)n * TN * d; ++i)
+        if (!(theta[i] >= 0.0 && theta[i] < INFINITY))
+            return fail(EPIPF_EINVAL, "theta[%zu][%zu][%zu][%zu]=%g: parameters must be finite and >= 0", i / (TN * d),
+                        i / ((size_t)N * d) % T, i / d % N, i % d, theta[i]);
+    for (size_t i = 0; i < (size_t)n * TN * C; ++i)
+        if (hidden[i] < 0)
+            return fail(EPIPF_EINVAL, "hidden[%zu][%zu][%zu][%zu]=%d: counts must be non-negative", i / (TN * C),
+                        i / ((size_t)N * C) % T, i / C % N, i % C, hidden[i]);
+    for (size_t i = 0; i < (size_t)n * TN; ++i)
+        if (ancestry[i] < 0 || ancestry[i] >= N)
+            return fail(EPIPF_EINVAL, "ancestry[%zu][%zu][%zu]=%d: ancestors must lie in [0, N)", i / TN, i / N % T, i % N,
+                        ancestry[i]);
+    std::vector<double> soa((size_t)n * TN * d);          // [n][T][N][d] -> [n][T][d][N]
+    for (size_t r = 0; r < (size_t)n * T; ++r)
+        for (int j = 0; j < N; ++j)
+            for (int k = 0; k < d; ++k) soa[(r * d + k) * N + j] = theta[(r * N + j) * d + k];
+    return walk_smooth_run(c, n, T, N, C, d, population_total, hidden, ancestry, soa.data(), lineage, lag, q, n_q, mean_out,
+                           quant_out, lineages_out);
 }
 
 int epipf_glibc_log(int64_t n, const double* x, double* out) {

@@ -350,6 +350,85 @@ class Engine:
                                                    ptr(quant), ptr(lineages)), "epipf_smooth_lag_history")
         return sums, quant, lineages
 
+    # ------------------------------------------------------------------ time-varying rates (epipf.walk)
+    def walk_filter(self, swarm, half_widths, probs, keys, filter_index, observations=False):
+        """epipf_walk_filter: the random-walk filter from the swarms [S, N, d] with chain s's half-widths
+        half_widths[s] ([S, d]).  Returns (log_zetas [S, T], status [S]); history(), smooth(), walk_history() and
+        walk_smooth() see the pass afterwards."""
+        swarm = np.ascontiguousarray(np.asarray(swarm, dtype=np.float64))
+        hw = np.ascontiguousarray(np.asarray(half_widths, dtype=np.float64))
+        if swarm.ndim != 3 or swarm.shape[1] != self.N:
+            raise ValueError(f"swarm must be [chains, {self.N}, d]")
+        S, _, d = swarm.shape
+        if hw.shape != (S, d):
+            raise ValueError(f"half_widths must be [{S}, {d}]")
+        probs = np.ascontiguousarray(np.broadcast_to(np.asarray(probs, dtype=np.float64), (S,)))
+        keys = np.ascontiguousarray(np.broadcast_to(np.asarray(keys, dtype=np.uint64), (S,)))
+        f = np.ascontiguousarray((np.broadcast_to(np.asarray(filter_index, dtype=np.uint64), (S,))
+                                  & np.uint64(0xFFFFFFFF)).astype(np.uint32))
+        lz = np.empty((S, self.T), dtype=np.float64)
+        st = np.empty(S, dtype=np.int32)
+        obs = _lib.OBS_NORMAL if observations else _lib.OBS_BINOMIAL
+        check(self._L.epipf_walk_filter(self._h, S, ptr(swarm), d, ptr(hw), obs, ptr(probs), ptr(keys), ptr(f), ptr(lz),
+                                        ptr(st)), "epipf_walk_filter")
+        self._last_n = S
+        self._last_status = st.copy()
+        _PARTICLE_STEPS[0] += S * self.N * self.T
+        return lz, st
+
+    def walk_history(self, n_chains=None):
+        """theta [n, T, N, d] of the last walk_filter (epipf_walk_history)."""
+        n = int(n_chains) if n_chains is not None else self._last_n or 1
+        d = 2 if self.model == _lib.SIR else 3
+        out = np.empty((max(n, 1), self.T, self.N, d), dtype=np.float64)
+        check(self._L.epipf_walk_history(self._h, n, ptr(out)), "epipf_walk_history")
+        return out
+
+    def walk_smooth(self, n_chains=None, quantiles=(0.05, 0.5, 0.95), lineage="genealogy", lag=None):
+        """epipf_walk_smooth on the last walk_filter's resident history: (mean [n, T, d + 1], quantiles
+        [n, Q, T, d + 1] or None, lineages [n, T]); the last column is R_t.  Rows of chains whose status was not OK are
+        NaN in mean and quantiles and 0 in lineages."""
+        from . import smoothing
+        lin, _, q = smoothing.check_options(lineage, "smoothing", quantiles)
+        lag = smoothing.check_lag(lag, "smoothing")
+        n = int(n_chains) if n_chains is not None else self._last_n or 1
+        V = (2 if self.model == _lib.SIR else 3) + 1
+        nq = 0 if q is None else q.size
+        rows = max(n, 1)
+        mean = np.zeros((rows, self.T, V), dtype=np.float64)
+        quant = np.zeros((rows, nq, self.T, V), dtype=np.float64) if nq else None
+        lineages = np.zeros((rows, self.T), dtype=np.int32)
+        check(self._L.epipf_walk_smooth(self._h, n, lin, -1 if lag is None else min(lag, 2**31 - 1), ptr(q), nq, ptr(mean),
+                                        ptr(quant), ptr(lineages)), "epipf_walk_smooth")
+        bad = self._last_status[:n] != _lib.STATUS_OK
+        mean[bad] = np.nan
+        if quant is not None:
+            quant[bad] = np.nan
+        return mean, quant, lineages
+
+    def walk_smooth_history(self, hidden, ancestry, theta, population_total, lineage, q, lag=None):
+        """epipf_walk_smooth_history on host arrays hidden [n, T, N, C] int32, ancestry [n, T, N] int32 and theta
+        [n, T, N, d] float64 (this engine's model and N are ignored); lineage is the library's id, q float64 [Q] or
+        None: (mean [n, T, d + 1], quantiles [n, Q, T, d + 1] or None, lineages [n, T])."""
+        from . import smoothing
+        lag = smoothing.check_lag(lag, "smoothing")
+        hidden = np.ascontiguousarray(hidden, dtype=np.int32)
+        ancestry = np.ascontiguousarray(ancestry, dtype=np.int32)
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        n, T, N, C = hidden.shape
+        d = theta.shape[-1]
+        if theta.shape != (n, T, N, d) or ancestry.shape != (n, T, N):
+            raise ValueError("hidden [n, T, N, C], ancestry [n, T, N] and theta [n, T, N, d] must agree")
+        nq = 0 if q is None else q.size
+        mean = np.zeros((n, T, d + 1), dtype=np.float64)
+        quant = np.zeros((n, nq, T, d + 1), dtype=np.float64) if nq else None
+        lineages = np.zeros((n, T), dtype=np.int32)
+        check(self._L.epipf_walk_smooth_history(self._h, n, T, N, C, d, ptr(hidden), ptr(ancestry), ptr(theta),
+                                                float(population_total), int(lineage),
+                                                -1 if lag is None else min(lag, 2**31 - 1), ptr(q), nq, ptr(mean),
+                                                ptr(quant), ptr(lineages)), "epipf_walk_smooth_history")
+        return mean, quant, lineages
+
     def resample(self, w, u):
         w = np.ascontiguousarray(np.asarray(w, dtype=np.float64))
         u = np.ascontiguousarray(np.asarray(u, dtype=np.float64))
