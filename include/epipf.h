@@ -36,6 +36,8 @@
  *   epipf_walk_filter / epipf_walk_history / epipf_walk_smooth / epipf_walk_smooth_history   no reference counterpart:
  *                        time-varying rates -- the filter of "theta follows a reflected random walk" with every day's
  *                        parameters kept, and smoothed daily beta, gamma and R_t as mean and quantiles
+ *   epipf_run_incidence  no reference counterpart: the filter on reported case counts (new infections, onsets, removals
+ *                        per day, with gaps and cumulated reports) instead of the compartments themselves
  *
  * The host wrapper (stochastic-epidemic-modelling_amd/epipf/) binds these with ctypes and keeps
  * the reference's Python signatures.  Conventions:
@@ -403,6 +405,33 @@ int epipf_walk_smooth_history(epipf_ctx* ctx, int n, int T, int N, int C, int d,
                               const int32_t* ancestry, const double* theta, double population_total, int lineage,
                               int lag, const double* q, int n_q, double* mean_out, double* quant_out,
                               int32_t* lineages_out);
+
+/* Incidence observations for the SIR and SEIR models: the filter weighted by reported transition counts
+ * instead of the compartments.  counts [D*F], one row per day d = 1..D for the interval (d-1, d], F = 2 columns for SIR
+ * (infections S' - S, removals R - R') and 3 for SEIR (exposures S' - S, onsets (I + R) - (I' + R'), removals R - R'),
+ * x' the particle's parent state and x its new one; NaN = not reported.  The pass has T = D + 2 rows: row 0 the initial
+ * draw (weight 1), rows 1..D the days, row D + 1 one more resampling on day D's weights and one more propagation, so
+ * log_zetas_out[s][D+1] is the log-likelihood of every report, log_zetas_out[s][1] is exactly 0, and the trajectories
+ * and the smoother see the last report.  With rep[p][k] = "counts row p column k is reported",
+ *   acc_p[j][k] = flow_p[j][k] + (cumulate && !rep[p-1][k] ? acc_{p-1}[a_p[j]][k] : 0),   acc_0 = 0
+ *   w_p[j]      = product over the k with rep[p][k], in column order from 1.0, of
+ *                 EPIPF_OBS_BINOMIAL: the binomial pmf of counts[p][k] out of acc_p[j][k] at probs[s]
+ *                 EPIPF_OBS_NORMAL:   the normal pdf of counts[p][k] at mean acc_p[j][k], sd probs[s] acc_p[j][k] + 1e-4
+ * (a row with nothing reported weighs 1).  cumulate = 0: a report counts its day alone; 1: everything since that
+ * column's previous report (ping-pong accumulator int32 [2][n_chains][F][N] on the device, allocated on first use,
+ * regrown when a call needs more, freed by epipf_destroy; EPIPF_ENOMEM names the bytes asked for, also when they exceed
+ * the budget EPIPF_INCIDENCE_ACC_BYTES of the environment at epipf_create).  Resampling is multinomial; Philox domains,
+ * counters, the SSA and the degeneracy rule are epipf_run's, and so are theta, keys, filter_index and active.
+ *   log_zetas_out [n_chains*(D+2)];  status_out [n_chains]
+ * The reports live in a device buffer of their own: the observations of epipf_set_observations are untouched (and not
+ * needed; epipf_set_population is).  The context's run length becomes D + 2: epipf_copy_history, epipf_path_sample,
+ * epipf_smooth and epipf_smooth_lag see the pass afterwards; epipf_walk_history is EPIPF_ESTATE after it.
+ * EPIPF_EINVAL, naming the first offending index: a subgroup context; D < 1 or D + 2 > t_max; a report that is infinite
+ * or negative, or (binomial) not an integer; an active chain's theta entry negative, NaN or infinite; an active chain's
+ * probs NaN, infinite, negative or (binomial) above 1. */
+int epipf_run_incidence(epipf_ctx* ctx, int n_chains, const double* theta, int d, int obs_model, const double* probs,
+                        const uint64_t* keys, const uint32_t* filter_index, const int32_t* active, const double* counts,
+                        int D, int cumulate, double* log_zetas_out, int32_t* status_out);
 
 /* The device's restatement of glibc's log (the reference's math.log / numpy legacy exponential),
  * evaluated on the host CPU with the same code and table: out[i] = log(x[i]) bit for bit for normal x[i] > 0.

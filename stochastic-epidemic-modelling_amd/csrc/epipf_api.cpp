@@ -22,6 +22,7 @@
 #include "abc_device.hpp"
 #include "epipf_if2.hpp"
 #include "epipf_if2_sub.hpp"
+#include "epipf_incidence.hpp"
 #include "epipf_internal.hpp"
 #include "epipf_smooth.hpp"
 #include "epipf_smooth_lag.hpp"
@@ -142,6 +143,14 @@ struct epipf_ctx {
     double* walk_theta = nullptr;
     size_t walk_bytes = 0;
     bool walk_valid = false;
+    // incidence observations (epipf_run_incidence): the reports [D + 2][F] in a buffer of their own (Y is
+    // not touched) and, for cumulated reports, the ping-pong accumulator int32 [2][chains][F][N]; both allocated on
+    // first use and regrown when a call needs more.  acc_limit: a budget for the accumulator in bytes
+    // (EPIPF_INCIDENCE_ACC_BYTES; 0: none), beyond which the call is EPIPF_ENOMEM without asking the device.
+    double* inc_counts = nullptr;
+    size_t inc_counts_n = 0;
+    int32_t* inc_acc = nullptr;
+    size_t inc_acc_bytes = 0, inc_acc_limit = 0;
 };
 
 // Lanes per particle for a run of n_chains filters.  The one-lane kernel needs ~20k waves per launch to fill the
@@ -343,7 +352,7 @@ static void free_ctx(epipf_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void* dev[] = {c->hidden, c->ancestry, c->res, c->chosen, c->traj, c->wraw, c->wloc, c->bsum,
-                   c->Y, c->lf, c->cp, c->logtab, c->scratch, c->abc, c->walk_theta};
+                   c->Y, c->lf, c->cp, c->logtab, c->scratch, c->abc, c->walk_theta, c->inc_counts, c->inc_acc};
     for (void* p : dev)
         if (p) (void)hipFree(p);
     void* host[] = {c->h_cp, c->h_res, c->h_traj};
@@ -421,6 +430,7 @@ int epipf_create(epipf_ctx** out, int device, int model, int groups, int n_parti
     if (const char* e = getenv("EPIPF_CLOCK_SLACK")) c->clock_slack = std::max(1.0f, std::min(1e12f, (float)atof(e)));
     if (const char* e = getenv("EPIPF_BAND_SLACK")) c->band_slack = std::max(1.0f, std::min(1e4f, (float)atof(e)));
     if (const char* e = getenv("EPIPF_TIE_SCALE")) c->tie_scale = std::max(1.0, std::min(1e300, atof(e)));
+    if (const char* e = getenv("EPIPF_INCIDENCE_ACC_BYTES")) c->inc_acc_limit = (size_t)std::max(0LL, atoll(e));
     if (const char* e = getenv("EPIPF_STREAMS")) c->n_streams = std::max(1, std::min(kMaxFilterStreams, atoi(e)));
     if (const char* e = getenv("EPIPF_LANES")) {
         const int w = atoi(e);
@@ -1620,6 +1630,157 @@ int epipf_walk_filter(epipf_ctx* c, int n_chains, const double* swarm_in, int d,
     c->have_run = true;
     c->walk_valid = true;
     trim_scratch(c);
+    return EPIPF_OK;
+}
+
+// ------------------------------------------------------------------------ incidence observations
+// The filter on reported transition counts: T = D + 2 rows (row 0 the initial draw, rows 1..D the days, row D + 1 one more
+// resampling on day D's weights), weights from the particles' flows (epipf_incidence.hpp).  hidden, ancestry, status and
+// log_zeta are the context's own and the run length becomes D + 2, so epipf_copy_history, epipf_path_sample, epipf_smooth
+// and epipf_smooth_lag see the pass afterwards.
+int epipf_run_incidence(epipf_ctx* c, int n_chains, const double* theta, int d, int obs_model, const double* probs,
+                        const uint64_t* keys, const uint32_t* filter_index, const int32_t* active, const double* counts,
+                        int D, int cumulate, double* log_zetas_out, int32_t* status_out) {
+    if (!c || !theta || !probs || !keys || !filter_index || !counts || !log_zetas_out || !status_out)
+        return fail(EPIPF_EINVAL, "NULL argument");
+    if (c->model != EPIPF_SIR && c->model != EPIPF_SEIR)
+        return fail(EPIPF_EINVAL, "incidence observations cover the SIR and SEIR models; the subgroup models are out of their scope");
+    if (!c->have_pop) return fail(EPIPF_ESTATE, "epipf_set_population was not called");
+    const int S = n_chains, N = c->N, F = incidence_flows(c->model);
+    if (S < 1 || S > c->max_chains) return fail(EPIPF_EINVAL, "n_chains=%d outside [1, max_chains=%d]", S, c->max_chains);
+    if (d != theta_dim(c->model, c->G)) return fail(EPIPF_EINVAL, "theta has %d entries per chain, model needs %d", d, theta_dim(c->model, c->G));
+    if (obs_model != EPIPF_OBS_BINOMIAL && obs_model != EPIPF_OBS_NORMAL) return fail(EPIPF_EINVAL, "bad obs_model %d", obs_model);
+    if (D < 1 || (long long)D + 2 > c->Tmax) return fail(EPIPF_EINVAL, "D=%d: D + 2 rows outside [3, t_max=%d]", D, c->Tmax);
+    const int T = D + 2;
+    std::vector<double> rows((size_t)T * F, NAN);
+    std::vector<uint8_t> rep((size_t)T, 0);
+    for (size_t i = 0; i < (size_t)D * F; ++i) {
+        const double y = counts[i];
+        if (std::isnan(y)) continue;                                     // not reported
+        if (std::isinf(y) || y < 0.0)
+            return fail(EPIPF_EINVAL, "counts[%zu][%zu]=%g: a report must be finite and >= 0 (NaN: not reported)", i / F, i % F, y);
+        if (obs_model == EPIPF_OBS_BINOMIAL && y != std::floor(y))
+            return fail(EPIPF_EINVAL, "counts[%zu][%zu]=%g: the binomial model needs integer reports", i / F, i % F, y);
+        rows[(size_t)F + i] = y;
+        rep[1 + i / F] |= (uint8_t)(1u << (i % F));
+    }
+    for (int ch = 0; ch < S; ++ch) {
+        const bool on = !active || active[ch];
+        ChainParam& q = c->h_cp[ch];
+        memset(&q, 0, sizeof q);
+        for (int i = 0; i < d; ++i) {
+            const double v = theta[(size_t)ch * d + i];
+            if (on && !(v >= 0.0 && v < INFINITY))
+                return fail(EPIPF_EINVAL, "theta[%d][%d]=%g: parameters must be finite and >= 0", ch, i, v);
+            set_theta(q, nullptr, i, v);
+        }
+        const double pr = probs[ch];
+        if (on && !(pr >= 0.0 && pr < INFINITY && (obs_model == EPIPF_OBS_NORMAL || pr <= 1.0)))
+            return fail(EPIPF_EINVAL, "probs[%d]=%g: %s", ch, pr,
+                        obs_model == EPIPF_OBS_NORMAL ? "the noise ratio must be finite and >= 0"
+                                                      : "the reporting probability must lie in [0, 1]");
+        set_chain_stream(c, q, pr, keys[ch], filter_index[ch]);
+        q.skip = on ? 0 : 1;
+        q.chosen = -1;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    c->walk_valid = false;                               // the history is this run's from here on
+    if (rows.size() > c->inc_counts_n) {
+        if (c->inc_counts) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->inc_counts); }
+        c->inc_counts = nullptr;
+        c->inc_counts_n = 0;
+        if (dalloc(&c->inc_counts, rows.size())) return EPIPF_ENOMEM;
+        c->inc_counts_n = rows.size();
+    }
+    const size_t acc_half = (size_t)S * F * N;
+    if (cumulate) {
+        const size_t need = 2 * sizeof(int32_t) * acc_half;
+        if (need > c->inc_acc_bytes) {
+            if (c->inc_acc_limit && need > c->inc_acc_limit)
+                return fail(EPIPF_ENOMEM, "the accumulator needs %zu bytes (2 x %d chains x %d columns x %d int32): over the budget of %zu bytes",
+                            need, S, F, N, c->inc_acc_limit);
+            if (c->inc_acc) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->inc_acc); }
+            c->inc_acc = nullptr;
+            c->inc_acc_bytes = 0;
+            if (hipMalloc((void**)&c->inc_acc, need) != hipSuccess) {
+                c->inc_acc = nullptr;
+                (void)hipGetLastError();
+                return fail(EPIPF_ENOMEM, "the accumulator needs %zu bytes (2 x %d chains x %d columns x %d int32): hipMalloc failed",
+                            need, S, F, N);
+            }
+            c->inc_acc_bytes = need;
+        }
+    }
+    // rows and rep stay alive past the stream synchronisation below
+    HIP_TRY(hipMemcpyAsync(c->cp, c->h_cp, sizeof(ChainParam) * S, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->inc_counts, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->log_zeta, 0xFF, sizeof(double) * (size_t)S * T, c->stream));   // rows never written read as NaN
+    const size_t b_counters = sizeof(unsigned long long) * (size_t)kCounterSlots * kCounterStride;
+    HIP_TRY(hipMemsetAsync(c->counters, 0, b_counters, c->stream));
+
+    IncidenceArgs a{};
+    StepArgs& s = a.s;
+    s.N = N; s.T = T; s.max_chains = c->max_chains; s.wg = 64; s.B = (N + 63) / 64; s.lanes = 1; s.lane_events = 1;
+    s.resample_mode = EPIPF_RESAMPLE_MULTINOMIAL; s.lf_max = c->lf_max;
+    s.count_events = c->profiling >= EPIPF_PROFILE_COUNTERS ? 1 : 0;
+    s.hist_stride = c->hist_stride; s.anc_stride = c->anc_stride; s.wstride = c->wstride; s.bstride = c->bstride;
+    s.seg = prefix_segment(s.B);
+    s.nseg = (s.B + s.seg - 1) / s.seg;
+    s.cert_k = cert_k(N, s.B, s.seg, 64);
+    s.Y = nullptr; s.lf = c->lf; s.logtab = c->logtab; s.cp = c->cp; s.hidden = c->hidden; s.ancestry = c->ancestry;
+    s.wraw = c->wraw; s.wloc = c->wloc; s.bsum = c->bsum; s.log_zeta = c->log_zeta; s.status = c->status; s.counters = c->counters;
+    s.xcd_map = c->xcd_map;
+    for (int g = 0; g < kMaxLaneG; ++g) { s.npop[g] = c->npop[g]; s.mu[g] = c->mu[g]; s.emu[g] = c->emu[g]; s.kmax[g] = c->kmax[g]; }
+    a.counts = c->inc_counts; a.acc = cumulate ? c->inc_acc : nullptr; a.acc_half = acc_half;
+
+    FilterStreams fs{};
+    fs.n = std::min(c->n_streams, S);
+    if (!ensure_streams(c, fs.n)) return fail(EPIPF_EHIP, "auxiliary stream creation failed");
+    fs.s[0] = c->stream;
+    if (fs.n > 1) HIP_TRY(hipEventRecord(c->fork, c->stream));    // the groups' inputs are on c->stream
+    for (int g = 1; g < fs.n; ++g) {
+        fs.s[g] = c->aux[g];
+        fs.join[g] = c->join[g];
+        HIP_TRY(hipStreamWaitEvent(c->aux[g], c->fork, 0));
+    }
+    c->last_groups = fs.n;
+    const hipError_t le = launch_incidence(a, c->model, obs_model, cumulate != 0, rep.data(), S, fs);
+    if (le != hipSuccess) return fail(EPIPF_EHIP, "kernel launch failed: %s", hipGetErrorString(le));
+    HIP_TRY(hipMemcpyAsync(log_zetas_out, c->log_zeta, sizeof(double) * (size_t)S * T, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(status_out, c->status, sizeof(int32_t) * S, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_counters, c->counters, b_counters, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemsetAsync(c->counters, 0, b_counters, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    unsigned long long tot[kNumCounters] = {};
+    for (int sl = 0; sl < kCounterSlots; ++sl)
+        for (int k = 0; k < kNumCounters; ++k) tot[k] += c->h_counters[(size_t)sl * kCounterStride + k];
+    c->stats.resample_fallbacks = (int64_t)tot[1];
+    if (s.count_events) {
+        c->stats.events = (int64_t)tot[0];
+        c->stats.lane_iterations = (int64_t)tot[2];
+        c->stats.wave_lane_slots = (int64_t)tot[3];
+        c->stats.ssa_exact_lanes = (int64_t)tot[4];
+        c->stats.ssa_exact_waves = (int64_t)tot[5];
+    }
+    // a chain that died at step p wrote -inf there and nothing after: its later rows are -inf as well; a skipped chain
+    // ran nothing: NaN throughout (epipf_run)
+    int n_active = 0;
+    for (int q = 0; q < S; ++q) {
+        n_active += status_out[q] != EPIPF_STATUS_SKIPPED;
+        for (int p = 0; p < T; ++p) {
+            double& v = log_zetas_out[(size_t)q * T + p];
+            if (status_out[q] == EPIPF_STATUS_SKIPPED) v = NAN;
+            else if (status_out[q] == EPIPF_STATUS_DEGENERATE && std::isnan(v)) v = -INFINITY;
+        }
+    }
+    c->stats.particle_steps += (int64_t)n_active * N * T;
+    c->stats.filters += n_active;
+    c->stats.last_lanes = 1;
+    c->stats.last_lane_events = 1;
+    c->stats.last_fused = 0;
+    c->last_chains = S;
+    c->last_T = T;
+    c->have_run = true;
     return EPIPF_OK;
 }
 

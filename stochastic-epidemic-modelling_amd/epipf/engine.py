@@ -93,7 +93,8 @@ class Engine:
         self._Y = None
         self._pop = None
         self.bound_to = None                             # token of the ChainSampler whose data is loaded (_bind)
-        self.T = 0
+        self.T = 0                                       # rows of the observations (set_observations)
+        self._run_T = None                               # rows of the last run, as the context holds them (last_T)
         self._last_n = None
 
     # ------------------------------------------------------------------ lifecycle
@@ -132,6 +133,13 @@ class Engine:
         self._pop = key
         self.bound_to = None
 
+    @property
+    def run_T(self):
+        """Rows of the last run's history: the observations' T after run / if2 / walk_filter, D + 2 after run_incidence
+        (before any run: T).  history(), path_sample(), smooth(), walk_history() and walk_smooth() are sized by it, as
+        the library writes them, whatever set_observations did since."""
+        return self.T if self._run_T is None else self._run_T
+
     # ------------------------------------------------------------------ the filter
     def run(self, thetas, probs, keys, filter_indices, observations=False, active=None, resample="multinomial",
             chosen=None):
@@ -160,9 +168,44 @@ class Engine:
                                             ptr(fidx), ptr(act), mode, ptr(ch), ptr(lz), ptr(st), ptr(tr)),
                   "epipf_run_sampled")
         self._last_n = n
+        self._run_T = self.T
         self._last_status = st.copy()                    # Engine.smooth: rows of chains that did not run are NaN
         _PARTICLE_STEPS[0] += (n if act is None else int(np.count_nonzero(act))) * self.N * self.T
         return (lz, st) if chosen is None else (lz, st, tr)
+
+    def run_incidence(self, thetas, probs, keys, filter_indices, counts, observations=False, cumulate=False,
+                      active=None):
+        """epipf_run_incidence: len(thetas) filters on the reported transition counts `counts` [D, F] (F = 2 for SIR:
+        infections, removals; 3 for SEIR: exposures, onsets, removals; NaN = not reported), shared by the chains.
+        Returns (log_zetas [n, D + 2], status [n]); run_T becomes D + 2 (T stays the observations'), and history(),
+        path_sample() and smooth() see the pass afterwards."""
+        thetas = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64))
+        if thetas.ndim != 2:
+            raise ValueError("thetas must be [chains, d]")
+        n = thetas.shape[0]
+        counts = np.ascontiguousarray(np.asarray(counts, dtype=np.float64))
+        F = 2 if self.model == _lib.SIR else 3
+        if counts.ndim != 2 or counts.shape[1] != F:
+            raise ValueError(f"counts must be [D, {F}] for this model")
+        D = counts.shape[0]
+        probs = np.ascontiguousarray(np.broadcast_to(np.asarray(probs, dtype=np.float64), (n,)))
+        keys = np.ascontiguousarray(np.broadcast_to(np.asarray(keys, dtype=np.uint64), (n,)))
+        fidx = np.ascontiguousarray((np.broadcast_to(np.asarray(filter_indices, dtype=np.uint64), (n,))
+                                     & np.uint64(0xFFFFFFFF)).astype(np.uint32))
+        act = None if active is None else np.ascontiguousarray(np.asarray(active, dtype=np.int32))
+        if act is not None and act.shape != (n,):
+            raise ValueError(f"active must have {n} entries")
+        lz = np.empty((n, D + 2), dtype=np.float64)
+        st = np.empty(n, dtype=np.int32)
+        obs = _lib.OBS_NORMAL if observations else _lib.OBS_BINOMIAL
+        check(self._L.epipf_run_incidence(self._h, n, ptr(thetas), thetas.shape[1], obs, ptr(probs), ptr(keys),
+                                          ptr(fidx), ptr(act), ptr(counts), D, 1 if cumulate else 0, ptr(lz), ptr(st)),
+              "epipf_run_incidence")
+        self._run_T = D + 2
+        self._last_n = n
+        self._last_status = st.copy()
+        _PARTICLE_STEPS[0] += (n if act is None else int(np.count_nonzero(act))) * self.N * (D + 2)
+        return lz, st
 
     def if2(self, swarm, half_widths, probs, keys, filter_index0, observations=False):
         """epipf_if2: iterated filtering from the swarms [S, N, d] with the half-width table [M, d], search s at filter
@@ -197,6 +240,7 @@ class Engine:
         check(getattr(self._L, entry)(self._h, S, M, ptr(swarm), d, ptr(hw), obs, ptr(probs), ptr(keys), ptr(f0),
                                       ptr(lz), ptr(mean), ptr(done), ptr(st)), entry)
         self._last_n = S
+        self._run_T = self.T
         self._last_status = st.copy()
         _PARTICLE_STEPS[0] += int(np.minimum(done + 1, M).sum()) * self.N * self.T
         return swarm, mean, lz, done, st
@@ -204,14 +248,14 @@ class Engine:
     def history(self, n_chains=None):
         """(hidden [n, T, N, C] int32, ancestry [n, T, N] int32) of the last run."""
         n = self._last_n if n_chains is None else int(n_chains)
-        hid = np.empty((n, self.T, self.N, self.C), dtype=np.int32)
-        anc = np.empty((n, self.T, self.N), dtype=np.int32)
+        hid = np.empty((n, self.run_T, self.N, self.C), dtype=np.int32)
+        anc = np.empty((n, self.run_T, self.N), dtype=np.int32)
         check(self._L.epipf_copy_history(self._h, n, ptr(hid), ptr(anc)), "epipf_copy_history")
         return hid, anc
 
     def path_sample(self, chosen):
         chosen = np.ascontiguousarray(np.asarray(chosen, dtype=np.int32).reshape(-1))
-        out = np.empty((chosen.size, self.T, self.C), dtype=np.int32)
+        out = np.empty((chosen.size, self.run_T, self.C), dtype=np.int32)
         check(self._L.epipf_path_sample(self._h, chosen.size, ptr(chosen), ptr(out)), "epipf_path_sample")
         return out
 
@@ -314,9 +358,9 @@ class Engine:
             bins = int(sum(self._pop[0])) + 1
         nq = 0 if q is None else q.size
         rows = max(n, 1)                                  # a bad n_chains is the library's EPIPF_EINVAL
-        sums = np.zeros((rows, self.T, self.C), dtype=np.int64)
-        lineages = np.zeros((rows, self.T), dtype=np.int32)
-        quant = np.zeros((rows, nq, self.T, self.C), dtype=np.int32) if nq else None
+        sums = np.zeros((rows, self.run_T, self.C), dtype=np.int64)
+        lineages = np.zeros((rows, self.run_T), dtype=np.int32)
+        quant = np.zeros((rows, nq, self.run_T, self.C), dtype=np.int32) if nq else None
         if lag is None:
             check(self._L.epipf_smooth(self._h, n, lin, knd, ptr(q), nq, int(bins) if nq else 0, ptr(sums), ptr(quant),
                                        ptr(lineages)), "epipf_smooth")
@@ -372,6 +416,7 @@ class Engine:
         check(self._L.epipf_walk_filter(self._h, S, ptr(swarm), d, ptr(hw), obs, ptr(probs), ptr(keys), ptr(f), ptr(lz),
                                         ptr(st)), "epipf_walk_filter")
         self._last_n = S
+        self._run_T = self.T
         self._last_status = st.copy()
         _PARTICLE_STEPS[0] += S * self.N * self.T
         return lz, st
@@ -380,7 +425,7 @@ class Engine:
         """theta [n, T, N, d] of the last walk_filter (epipf_walk_history)."""
         n = int(n_chains) if n_chains is not None else self._last_n or 1
         d = 2 if self.model == _lib.SIR else 3
-        out = np.empty((max(n, 1), self.T, self.N, d), dtype=np.float64)
+        out = np.empty((max(n, 1), self.run_T, self.N, d), dtype=np.float64)
         check(self._L.epipf_walk_history(self._h, n, ptr(out)), "epipf_walk_history")
         return out
 
@@ -395,9 +440,9 @@ class Engine:
         V = (2 if self.model == _lib.SIR else 3) + 1
         nq = 0 if q is None else q.size
         rows = max(n, 1)
-        mean = np.zeros((rows, self.T, V), dtype=np.float64)
-        quant = np.zeros((rows, nq, self.T, V), dtype=np.float64) if nq else None
-        lineages = np.zeros((rows, self.T), dtype=np.int32)
+        mean = np.zeros((rows, self.run_T, V), dtype=np.float64)
+        quant = np.zeros((rows, nq, self.run_T, V), dtype=np.float64) if nq else None
+        lineages = np.zeros((rows, self.run_T), dtype=np.int32)
         check(self._L.epipf_walk_smooth(self._h, n, lin, -1 if lag is None else min(lag, 2**31 - 1), ptr(q), nq, ptr(mean),
                                         ptr(quant), ptr(lineages)), "epipf_walk_smooth")
         bad = self._last_status[:n] != _lib.STATUS_OK
