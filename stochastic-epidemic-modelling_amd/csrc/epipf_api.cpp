@@ -385,6 +385,79 @@ static bool ensure_streams(epipf_ctx* c, int n) {
     return true;
 }
 
+// The per-particle filters' inputs: half_widths [rows][d] and swarm [S][N][d], every entry finite and >= 0.
+static int check_swarm(const double* half_widths, size_t rows, const double* swarm, size_t S, int N, int d) {
+    for (size_t i = 0; i < rows * d; ++i)
+        if (!(half_widths[i] >= 0.0 && half_widths[i] < INFINITY))
+            return fail(EPIPF_EINVAL, "half_widths[%zu][%zu]=%g: half-widths must be finite and >= 0", i / d, i % d, half_widths[i]);
+    for (size_t i = 0; i < S * N * d; ++i)
+        if (!(swarm[i] >= 0.0 && swarm[i] < INFINITY))
+            return fail(EPIPF_EINVAL, "swarm[%zu][%zu][%zu]=%g: parameters must be finite and >= 0", i / ((size_t)N * d),
+                        i / d % N, i % d, swarm[i]);
+    return EPIPF_OK;
+}
+
+// The fields of a filter launch's arguments that follow from the context alone: sizes, strides, tables, the context's
+// own buffers and the constants of the initial-state draw.  The caller chooses the layout (wg, B, lanes, seg, nseg,
+// cert_k) and the resampling mode.
+static void step_args_of(const epipf_ctx* c, StepArgs& a) {
+    a.N = c->N; a.T = c->T; a.max_chains = c->max_chains; a.lf_max = c->lf_max;
+    a.count_events = c->profiling >= EPIPF_PROFILE_COUNTERS ? 1 : 0;
+    a.hist_stride = c->hist_stride; a.anc_stride = c->anc_stride; a.wstride = c->wstride; a.bstride = c->bstride;
+    a.Y = c->Y; a.lf = c->lf; a.logtab = c->logtab; a.cp = c->cp; a.hidden = c->hidden; a.ancestry = c->ancestry;
+    a.wraw = c->wraw; a.wloc = c->wloc; a.bsum = c->bsum; a.log_zeta = c->log_zeta; a.status = c->status;
+    a.counters = c->counters;
+    a.xcd_map = c->xcd_map;
+    for (int g = 0; g < kMaxLaneG; ++g) { a.npop[g] = c->npop[g]; a.mu[g] = c->mu[g]; a.emu[g] = c->emu[g]; a.kmax[g] = c->kmax[g]; }
+}
+
+// The same for the filters that always run one lane per particle on 64-particle blocks with multinomial resampling
+// (iterated filtering, the random-walk filter, incidence observations), T rows long.
+static void one_lane_step_args(const epipf_ctx* c, int T, StepArgs& s) {
+    step_args_of(c, s);
+    s.T = T; s.wg = 64; s.B = (c->N + 63) / 64; s.lanes = 1; s.lane_events = 1;
+    s.resample_mode = EPIPF_RESAMPLE_MULTINOMIAL;
+    s.seg = prefix_segment(s.B);
+    s.nseg = (s.B + s.seg - 1) / s.seg;
+    s.cert_k = cert_k(c->N, s.B, s.seg, 64);
+}
+
+// The streams of a run in n chain groups: group 0 on c->stream, where the groups' inputs are; the others wait for it.
+// Created on first use, not with the context: HIP maps streams onto its few hardware queues in creation order, so
+// contexts that each run one group (run_pipelined) get one stream each and land on different queues.
+static int fork_streams(epipf_ctx* c, int n, FilterStreams& fs) {
+    fs.n = n;
+    if (!ensure_streams(c, fs.n)) return fail(EPIPF_EHIP, "auxiliary stream creation failed");
+    fs.s[0] = c->stream;
+    if (fs.n > 1) HIP_TRY(hipEventRecord(c->fork, c->stream));
+    for (int g = 1; g < fs.n; ++g) {
+        fs.s[g] = c->aux[g];
+        fs.join[g] = c->join[g];
+        HIP_TRY(hipStreamWaitEvent(c->aux[g], c->fork, 0));
+    }
+    c->last_groups = fs.n;
+    return EPIPF_OK;
+}
+
+// The device counters of the last run, copied to c->h_counters, summed over their slots into the statistics.
+// resample_fallbacks is counted at every profiling level.  epipf_run reports every counter as it stands (events and
+// ambiguous both true); the other filters report the event counters only where their kernels counted them
+// (count_events) and never touch resample_ref_ambiguous, which only the plain filter counts.
+static void harvest_counters(epipf_ctx* c, bool events, bool ambiguous) {
+    unsigned long long tot[kNumCounters] = {};
+    for (int sl = 0; sl < kCounterSlots; ++sl)
+        for (int k = 0; k < kNumCounters; ++k) tot[k] += c->h_counters[(size_t)sl * kCounterStride + k];
+    c->stats.resample_fallbacks = (int64_t)tot[1];
+    if (events) {
+        c->stats.events = (int64_t)tot[0];
+        c->stats.lane_iterations = (int64_t)tot[2];
+        c->stats.wave_lane_slots = (int64_t)tot[3];
+        c->stats.ssa_exact_lanes = (int64_t)tot[4];
+        c->stats.ssa_exact_waves = (int64_t)tot[5];
+    }
+    if (ambiguous) c->stats.resample_ref_ambiguous = (int64_t)tot[6];
+}
+
 extern "C" {
 
 const char* epipf_last_error(void) { return g_err.c_str(); }
@@ -637,15 +710,14 @@ static int run_impl(epipf_ctx* c, int n_chains, const double* theta, int d, int 
                                sizeof(WideParam) * n_chains, hipMemcpyHostToDevice, c->stream));
 
     StepArgs a{};
-    a.N = c->N; a.T = c->T; a.max_chains = c->max_chains;
+    step_args_of(c, a);
     bool tune_timed = false, tuning = false;
     const int fusedW = pick_fused(c) && fused_decide(c, obs_model, n_chains, tune_timed, tuning) ? pick_fused(c) : 0;
     a.lanes = fusedW ? fusedW : pick_lanes(c, n_chains);
     a.wg = fusedW ? 64 : pick_block(c, a.lanes);
     a.B = (c->N + a.wg - 1) / a.wg;
     a.group_lone = fusedW ? 0 : pick_group_lone(c, a, n_chains);
-    a.resample_mode = resample_mode; a.count_events = c->profiling >= EPIPF_PROFILE_COUNTERS ? 1 : 0; a.lf_max = c->lf_max;
-    a.hist_stride = c->hist_stride; a.anc_stride = c->anc_stride; a.wstride = c->wstride; a.bstride = c->bstride;
+    a.resample_mode = resample_mode;
     // S blocks per prefix segment: 1 (every block sum in LDS) for lane-group runs on 16-particle blocks up to
     // kMaxFlatGroupBlocks, else the smallest power of two with at most kMaxSegments segments
     // The 16-particle layout sums the step total in the 64-particle layout's order (scan_block_sums16): its segments are
@@ -659,11 +731,7 @@ static int run_impl(epipf_ctx* c, int n_chains, const double* theta, int d, int 
     // the reference-ambiguity test runs with the other device counters (bench.py's untimed counters iteration, the
     // parity tests); ref_k = 0 switches it off in the timed, production launches
     a.ref_k = a.count_events ? 2.0 * ref_pmf_envelope(obs_model, c->lf_max) * (1.0 + 0x1.0p-10) : 0.0;
-    a.Y = c->Y; a.lf = c->lf; a.logtab = c->logtab; a.cp = c->cp; a.hidden = c->hidden; a.ancestry = c->ancestry;
-    a.wraw = c->wraw; a.wloc = c->wloc; a.bsum = c->bsum; a.log_zeta = c->log_zeta; a.status = c->status;
-    a.counters = c->counters;
     a.lane_events = pick_lane_events(c, a.lanes);
-    a.xcd_map = c->xcd_map;
     if (a.lanes > 1 && !group_shape_supported(a.lanes, a.lane_events))
         return fail(EPIPF_EINVAL, "no lane-group kernel for %d lanes x %d events", a.lanes, a.lane_events);
     c->stats.last_lanes = a.lanes;
@@ -676,22 +744,11 @@ static int run_impl(epipf_ctx* c, int n_chains, const double* theta, int d, int 
         a.fused_y = base + yb <= kFusedLdsLimit;
         a.fused_lf = a.lf_max >= 0 && base + (a.fused_y ? yb : 0) + lb <= kFusedLdsLimit;
     }
-    for (int g = 0; g < kMaxLaneG; ++g) { a.npop[g] = c->npop[g]; a.mu[g] = c->mu[g]; a.emu[g] = c->emu[g]; a.kmax[g] = c->kmax[g]; }
 
     EPIPF_RANGE_PUSH("epipf_run");
     struct RangeEnd { ~RangeEnd() { EPIPF_RANGE_POP(); } } range_end;
     FilterStreams fs{};
-    fs.n = fusedW ? 1 : std::min(c->n_streams, n_chains);
-    // Created on first use, not with the context: HIP maps streams onto its few hardware queues in creation order,
-    // so contexts that each run one group (run_pipelined) get one stream each and land on different queues.
-    if (!ensure_streams(c, fs.n)) return fail(EPIPF_EHIP, "auxiliary stream creation failed");
-    fs.s[0] = c->stream;
-    if (fs.n > 1) HIP_TRY(hipEventRecord(c->fork, c->stream));    // the groups' inputs are on c->stream
-    for (int g = 1; g < fs.n; ++g) {
-        fs.s[g] = c->aux[g];
-        fs.join[g] = c->join[g];
-        HIP_TRY(hipStreamWaitEvent(c->aux[g], c->fork, 0));
-    }
+    if (const int e = fork_streams(c, fusedW ? 1 : std::min(c->n_streams, n_chains), fs)) return e;
     fs.ev_init = (c->profiling || tuning) ? c->ev[0] : nullptr;   // the path choice times the device span
     fs.ev_step0 = c->profiling ? c->ev[1] : nullptr;
     fs.ev_end = (c->profiling || tuning) ? c->ev[2] : nullptr;
@@ -699,7 +756,6 @@ static int run_impl(epipf_ctx* c, int n_chains, const double* theta, int d, int 
         fs.g_begin[g] = c->profiling ? c->gb[g] : nullptr;
         fs.g_end[g] = c->profiling ? c->ge[g] : nullptr;
     }
-    c->last_groups = fs.n;
     hipError_t le = fusedW ? launch_fused_run(a, c, obs_model, n_chains, fs)
                            : launch_filter(a, c->model, c->G, obs_model, n_chains, fs);
     if (le != hipSuccess) return fail(EPIPF_EHIP, "kernel launch failed: %s", hipGetErrorString(le));
@@ -755,16 +811,7 @@ static int run_impl(epipf_ctx* c, int n_chains, const double* theta, int d, int 
             c->stats.step_kernel_launches += fusedW ? 1 : c->T - 1;
         }
     }
-    unsigned long long tot[kNumCounters] = {};
-    for (int sl = 0; sl < kCounterSlots; ++sl)
-        for (int k = 0; k < kNumCounters; ++k) tot[k] += c->h_counters[(size_t)sl * kCounterStride + k];
-    c->stats.events = (int64_t)tot[0];
-    c->stats.resample_fallbacks = (int64_t)tot[1];
-    c->stats.lane_iterations = (int64_t)tot[2];
-    c->stats.wave_lane_slots = (int64_t)tot[3];
-    c->stats.ssa_exact_lanes = (int64_t)tot[4];
-    c->stats.ssa_exact_waves = (int64_t)tot[5];
-    c->stats.resample_ref_ambiguous = (int64_t)tot[6];
+    harvest_counters(c, true, true);
     c->stats.particle_steps += (int64_t)n_active * c->N * c->T;
     c->stats.filters += n_active;
     c->last_chains = n_chains;
@@ -1363,13 +1410,7 @@ static int if2_impl(epipf_ctx* c, bool subgroups, int n_searches, int iterations
     if (S < 1 || S > c->max_chains) return fail(EPIPF_EINVAL, "n_searches=%d outside [1, max_chains=%d]", S, c->max_chains);
     if (M < 1) return fail(EPIPF_EINVAL, "iterations=%d must be >= 1", M);
     if (obs_model != EPIPF_OBS_BINOMIAL && obs_model != EPIPF_OBS_NORMAL) return fail(EPIPF_EINVAL, "bad obs_model %d", obs_model);
-    for (size_t i = 0; i < (size_t)M * d; ++i)
-        if (!(half_widths[i] >= 0.0 && half_widths[i] < INFINITY))
-            return fail(EPIPF_EINVAL, "half_widths[%zu][%zu]=%g: half-widths must be finite and >= 0", i / d, i % d, half_widths[i]);
-    for (size_t i = 0; i < (size_t)S * N * d; ++i)
-        if (!(swarm_inout[i] >= 0.0 && swarm_inout[i] < INFINITY))
-            return fail(EPIPF_EINVAL, "swarm[%zu][%zu][%zu]=%g: parameters must be finite and >= 0", i / ((size_t)N * d),
-                        i / d % N, i % d, swarm_inout[i]);
+    if (const int e = check_swarm(half_widths, (size_t)M, swarm_inout, (size_t)S, N, d)) return e;
     for (int s = 0; s < S; ++s) {
         ChainParam& q = c->h_cp[s];
         memset(&q, 0, sizeof q);                         // theta is the particles' own (the swarm)
@@ -1405,30 +1446,12 @@ static int if2_impl(epipf_ctx* c, bool subgroups, int n_searches, int iterations
 
     If2Args a{};
     StepArgs& s = a.s;
-    s.N = N; s.T = T; s.max_chains = c->max_chains; s.wg = 64; s.B = (N + 63) / 64; s.lanes = 1; s.lane_events = 1;
-    s.resample_mode = EPIPF_RESAMPLE_MULTINOMIAL; s.lf_max = c->lf_max;
-    s.count_events = c->profiling >= EPIPF_PROFILE_COUNTERS ? 1 : 0;
-    s.hist_stride = c->hist_stride; s.anc_stride = c->anc_stride; s.wstride = c->wstride; s.bstride = c->bstride;
-    s.seg = prefix_segment(s.B);
-    s.nseg = (s.B + s.seg - 1) / s.seg;
-    s.cert_k = cert_k(N, s.B, s.seg, 64);
-    s.Y = c->Y; s.lf = c->lf; s.logtab = c->logtab; s.cp = c->cp; s.hidden = c->hidden; s.ancestry = c->ancestry;
-    s.wraw = c->wraw; s.wloc = c->wloc; s.bsum = c->bsum; s.log_zeta = d_lz; s.status = c->status; s.counters = c->counters;
-    s.xcd_map = c->xcd_map;
-    for (int g = 0; g < kMaxLaneG; ++g) { s.npop[g] = c->npop[g]; s.mu[g] = c->mu[g]; s.emu[g] = c->emu[g]; s.kmax[g] = c->kmax[g]; }
+    one_lane_step_args(c, T, s);
+    s.log_zeta = d_lz;                                   // [M][max_chains][T], a row block per iteration
     a.d = d; a.M = M; a.swarm = d_swarm; a.start = d_start; a.mean = d_mean; a.done = d_done;
 
     FilterStreams fs{};
-    fs.n = std::min(c->n_streams, S);
-    if (!ensure_streams(c, fs.n)) return fail(EPIPF_EHIP, "auxiliary stream creation failed");
-    fs.s[0] = c->stream;
-    if (fs.n > 1) HIP_TRY(hipEventRecord(c->fork, c->stream));    // the groups' inputs are on c->stream
-    for (int g = 1; g < fs.n; ++g) {
-        fs.s[g] = c->aux[g];
-        fs.join[g] = c->join[g];
-        HIP_TRY(hipStreamWaitEvent(c->aux[g], c->fork, 0));
-    }
-    c->last_groups = fs.n;
+    if (const int e = fork_streams(c, std::min(c->n_streams, S), fs)) return e;
     hipError_t le = subgroups ? launch_if2_sub(a, c->model, c->G, obs_model, S, half_widths, fs)
                               : launch_if2(a, c->model, obs_model, S, half_widths, fs);
     if (le != hipSuccess) return fail(EPIPF_EHIP, "kernel launch failed: %s", hipGetErrorString(le));
@@ -1441,17 +1464,7 @@ static int if2_impl(epipf_ctx* c, bool subgroups, int n_searches, int iterations
     HIP_TRY(hipMemcpyAsync(c->h_counters, c->counters, b_counters, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemsetAsync(c->counters, 0, b_counters, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    unsigned long long tot[kNumCounters] = {};
-    for (int sl = 0; sl < kCounterSlots; ++sl)
-        for (int k = 0; k < kNumCounters; ++k) tot[k] += c->h_counters[(size_t)sl * kCounterStride + k];
-    c->stats.resample_fallbacks = (int64_t)tot[1];       // counted at every profiling level, as in epipf_run
-    if (s.count_events) {
-        c->stats.events = (int64_t)tot[0];
-        c->stats.lane_iterations = (int64_t)tot[2];
-        c->stats.wave_lane_slots = (int64_t)tot[3];
-        c->stats.ssa_exact_lanes = (int64_t)tot[4];
-        c->stats.ssa_exact_waves = (int64_t)tot[5];
-    }
+    harvest_counters(c, s.count_events != 0, false);
     int64_t passes = 0;
     for (int q = 0; q < S; ++q) {
         for (int j = 0; j < N; ++j)
@@ -1526,13 +1539,7 @@ int epipf_walk_filter(epipf_ctx* c, int n_chains, const double* swarm_in, int d,
     if (d != theta_dim(c->model, c->G)) return fail(EPIPF_EINVAL, "theta has %d entries per particle, model needs %d", d, theta_dim(c->model, c->G));
     if (S < 1 || S > c->max_chains) return fail(EPIPF_EINVAL, "n_chains=%d outside [1, max_chains=%d]", S, c->max_chains);
     if (obs_model != EPIPF_OBS_BINOMIAL && obs_model != EPIPF_OBS_NORMAL) return fail(EPIPF_EINVAL, "bad obs_model %d", obs_model);
-    for (size_t i = 0; i < (size_t)S * d; ++i)
-        if (!(half_widths[i] >= 0.0 && half_widths[i] < INFINITY))
-            return fail(EPIPF_EINVAL, "half_widths[%zu][%zu]=%g: half-widths must be finite and >= 0", i / d, i % d, half_widths[i]);
-    for (size_t i = 0; i < (size_t)S * N * d; ++i)
-        if (!(swarm_in[i] >= 0.0 && swarm_in[i] < INFINITY))
-            return fail(EPIPF_EINVAL, "swarm[%zu][%zu][%zu]=%g: parameters must be finite and >= 0", i / ((size_t)N * d),
-                        i / d % N, i % d, swarm_in[i]);
+    if (const int e = check_swarm(half_widths, (size_t)S, swarm_in, (size_t)S, N, d)) return e;
     for (int s = 0; s < S; ++s) {
         ChainParam& q = c->h_cp[s];
         memset(&q, 0, sizeof q);                         // theta is the particles' own
@@ -1573,30 +1580,11 @@ int epipf_walk_filter(epipf_ctx* c, int n_chains, const double* swarm_in, int d,
 
     WalkArgs a{};
     StepArgs& s = a.s;
-    s.N = N; s.T = T; s.max_chains = c->max_chains; s.wg = 64; s.B = (N + 63) / 64; s.lanes = 1; s.lane_events = 1;
-    s.resample_mode = EPIPF_RESAMPLE_MULTINOMIAL; s.lf_max = c->lf_max;
-    s.count_events = c->profiling >= EPIPF_PROFILE_COUNTERS ? 1 : 0;
-    s.hist_stride = c->hist_stride; s.anc_stride = c->anc_stride; s.wstride = c->wstride; s.bstride = c->bstride;
-    s.seg = prefix_segment(s.B);
-    s.nseg = (s.B + s.seg - 1) / s.seg;
-    s.cert_k = cert_k(N, s.B, s.seg, 64);
-    s.Y = c->Y; s.lf = c->lf; s.logtab = c->logtab; s.cp = c->cp; s.hidden = c->hidden; s.ancestry = c->ancestry;
-    s.wraw = c->wraw; s.wloc = c->wloc; s.bsum = c->bsum; s.log_zeta = c->log_zeta; s.status = c->status; s.counters = c->counters;
-    s.xcd_map = c->xcd_map;
-    for (int g = 0; g < kMaxLaneG; ++g) { s.npop[g] = c->npop[g]; s.mu[g] = c->mu[g]; s.emu[g] = c->emu[g]; s.kmax[g] = c->kmax[g]; }
+    one_lane_step_args(c, T, s);
     a.d = d; a.hw = d_hw; a.start = d_start; a.hist = c->walk_theta; a.chain_stride = stride;
 
     FilterStreams fs{};
-    fs.n = std::min(c->n_streams, S);
-    if (!ensure_streams(c, fs.n)) return fail(EPIPF_EHIP, "auxiliary stream creation failed");
-    fs.s[0] = c->stream;
-    if (fs.n > 1) HIP_TRY(hipEventRecord(c->fork, c->stream));    // the groups' inputs are on c->stream
-    for (int g = 1; g < fs.n; ++g) {
-        fs.s[g] = c->aux[g];
-        fs.join[g] = c->join[g];
-        HIP_TRY(hipStreamWaitEvent(c->aux[g], c->fork, 0));
-    }
-    c->last_groups = fs.n;
+    if (const int e = fork_streams(c, std::min(c->n_streams, S), fs)) return e;
     const hipError_t le = launch_walk(a, c->model, obs_model, S, fs);
     if (le != hipSuccess) return fail(EPIPF_EHIP, "kernel launch failed: %s", hipGetErrorString(le));
     HIP_TRY(hipMemcpyAsync(log_zetas_out, c->log_zeta, sizeof(double) * (size_t)S * T, hipMemcpyDeviceToHost, c->stream));
@@ -1604,17 +1592,7 @@ int epipf_walk_filter(epipf_ctx* c, int n_chains, const double* swarm_in, int d,
     HIP_TRY(hipMemcpyAsync(c->h_counters, c->counters, b_counters, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemsetAsync(c->counters, 0, b_counters, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    unsigned long long tot[kNumCounters] = {};
-    for (int sl = 0; sl < kCounterSlots; ++sl)
-        for (int k = 0; k < kNumCounters; ++k) tot[k] += c->h_counters[(size_t)sl * kCounterStride + k];
-    c->stats.resample_fallbacks = (int64_t)tot[1];
-    if (s.count_events) {
-        c->stats.events = (int64_t)tot[0];
-        c->stats.lane_iterations = (int64_t)tot[2];
-        c->stats.wave_lane_slots = (int64_t)tot[3];
-        c->stats.ssa_exact_lanes = (int64_t)tot[4];
-        c->stats.ssa_exact_waves = (int64_t)tot[5];
-    }
+    harvest_counters(c, s.count_events != 0, false);
     // a chain that died at step p wrote -inf there and nothing after: its later days are -inf as well
     for (int q = 0; q < S; ++q)
         if (status_out[q] == EPIPF_STATUS_DEGENERATE)
@@ -1720,30 +1698,12 @@ int epipf_run_incidence(epipf_ctx* c, int n_chains, const double* theta, int d, 
 
     IncidenceArgs a{};
     StepArgs& s = a.s;
-    s.N = N; s.T = T; s.max_chains = c->max_chains; s.wg = 64; s.B = (N + 63) / 64; s.lanes = 1; s.lane_events = 1;
-    s.resample_mode = EPIPF_RESAMPLE_MULTINOMIAL; s.lf_max = c->lf_max;
-    s.count_events = c->profiling >= EPIPF_PROFILE_COUNTERS ? 1 : 0;
-    s.hist_stride = c->hist_stride; s.anc_stride = c->anc_stride; s.wstride = c->wstride; s.bstride = c->bstride;
-    s.seg = prefix_segment(s.B);
-    s.nseg = (s.B + s.seg - 1) / s.seg;
-    s.cert_k = cert_k(N, s.B, s.seg, 64);
-    s.Y = nullptr; s.lf = c->lf; s.logtab = c->logtab; s.cp = c->cp; s.hidden = c->hidden; s.ancestry = c->ancestry;
-    s.wraw = c->wraw; s.wloc = c->wloc; s.bsum = c->bsum; s.log_zeta = c->log_zeta; s.status = c->status; s.counters = c->counters;
-    s.xcd_map = c->xcd_map;
-    for (int g = 0; g < kMaxLaneG; ++g) { s.npop[g] = c->npop[g]; s.mu[g] = c->mu[g]; s.emu[g] = c->emu[g]; s.kmax[g] = c->kmax[g]; }
+    one_lane_step_args(c, T, s);
+    s.Y = nullptr;                                       // the reports are a.counts
     a.counts = c->inc_counts; a.acc = cumulate ? c->inc_acc : nullptr; a.acc_half = acc_half;
 
     FilterStreams fs{};
-    fs.n = std::min(c->n_streams, S);
-    if (!ensure_streams(c, fs.n)) return fail(EPIPF_EHIP, "auxiliary stream creation failed");
-    fs.s[0] = c->stream;
-    if (fs.n > 1) HIP_TRY(hipEventRecord(c->fork, c->stream));    // the groups' inputs are on c->stream
-    for (int g = 1; g < fs.n; ++g) {
-        fs.s[g] = c->aux[g];
-        fs.join[g] = c->join[g];
-        HIP_TRY(hipStreamWaitEvent(c->aux[g], c->fork, 0));
-    }
-    c->last_groups = fs.n;
+    if (const int e = fork_streams(c, std::min(c->n_streams, S), fs)) return e;
     const hipError_t le = launch_incidence(a, c->model, obs_model, cumulate != 0, rep.data(), S, fs);
     if (le != hipSuccess) return fail(EPIPF_EHIP, "kernel launch failed: %s", hipGetErrorString(le));
     HIP_TRY(hipMemcpyAsync(log_zetas_out, c->log_zeta, sizeof(double) * (size_t)S * T, hipMemcpyDeviceToHost, c->stream));
@@ -1751,17 +1711,7 @@ int epipf_run_incidence(epipf_ctx* c, int n_chains, const double* theta, int d, 
     HIP_TRY(hipMemcpyAsync(c->h_counters, c->counters, b_counters, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemsetAsync(c->counters, 0, b_counters, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    unsigned long long tot[kNumCounters] = {};
-    for (int sl = 0; sl < kCounterSlots; ++sl)
-        for (int k = 0; k < kNumCounters; ++k) tot[k] += c->h_counters[(size_t)sl * kCounterStride + k];
-    c->stats.resample_fallbacks = (int64_t)tot[1];
-    if (s.count_events) {
-        c->stats.events = (int64_t)tot[0];
-        c->stats.lane_iterations = (int64_t)tot[2];
-        c->stats.wave_lane_slots = (int64_t)tot[3];
-        c->stats.ssa_exact_lanes = (int64_t)tot[4];
-        c->stats.ssa_exact_waves = (int64_t)tot[5];
-    }
+    harvest_counters(c, s.count_events != 0, false);
     // a chain that died at step p wrote -inf there and nothing after: its later rows are -inf as well; a skipped chain
     // ran nothing: NaN throughout (epipf_run)
     int n_active = 0;

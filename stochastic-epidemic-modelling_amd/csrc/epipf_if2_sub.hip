@@ -1,8 +1,10 @@
 // epipf_if2_sub.hip -- the iterated-filtering kernels of the subgroup models (G = 2..4) for MI355X (gfx950) and their
 // launcher.
 //
-// if2_sub_init_kernel / if2_sub_step_kernel are if2_init_kernel / if2_step_kernel (epipf_if2.hip) with G groups: one lane
-// per particle, one wave per block, the filter's grid, weights, scans and certified resampling search.  theta is
+// if2_sub_init_kernel / if2_sub_step_kernel filter with theta per particle and G groups: one lane per particle, one wave
+// per block, on the shared phases of epipf_step.hpp (step_total, step_ancestor, step_count, step_store_weights,
+// step_degenerate, step_log_zeta, init_state, init_weights) with IF2's status rule and filter index (epipf_if2.hip).
+// theta is
 // beta[G][G] row-major then gamma, D = G*G + 1 components per particle: gathered from the ancestor out of the
 // component-major swarm, jittered on domain 7 << 24 (component c from block c / 2), stored, and used as the lane's own
 // rates (a per-lane ChainParam copy: theta for the exact loop, thetaf for the certified f32 loop).  The loops over the
@@ -61,10 +63,7 @@ __global__ __launch_bounds__(64) void if2_sub_init_kernel(If2SubArgs a) {
     for (int c = 0; c < C; ++c) x[c] = 0.0;
     if (j < s.N) {
         init_particle<MODEL, G>(s, cp, j, x);                            // pmcmc.py:156-175
-        int32_t* h = s.hidden + (size_t)chain * s.hist_stride + (size_t)j * C;
-#pragma unroll
-        for (int c = 0; c < C; ++c) h[c] = (int32_t)x[c];
-        s.ancestry[(size_t)chain * s.anc_stride + j] = 0;
+        init_state<C>(s, chain, j, x);
         double th[D];
 #pragma unroll
         for (int c = 0; c < D; ++c) th[c] = a.start[((size_t)chain * D + c) * s.N + j];
@@ -72,18 +71,10 @@ __global__ __launch_bounds__(64) void if2_sub_init_kernel(If2SubArgs a) {
 #pragma unroll
         for (int c = 0; c < D; ++c) a.swarm[((size_t)chain * D + c) * s.N + j] = th[c];   // buffer 0
     }
-    if (bp.b == 0 && threadIdx.x == 0) s.log_zeta[(size_t)chain * s.T] = 0.0;
-    if (s.T > 1) {
-        double w = 0.0;
-        if (j < s.N)
-            w = particle_weight<MODEL, G, OBS>(x, s.Y, cp, s.cp + chain, s.lf, s.lf_max,
-                                               s.hidden + (size_t)chain * s.hist_stride + (size_t)j * C);
-        const size_t wbase = (size_t)chain * s.wstride;                  // buffer 0
-        const double loc = block_inclusive_scan<WG>(w, smem);
-        s.wraw[wbase + j] = w;
-        s.wloc[wbase + j] = loc;
-        if ((int)threadIdx.x == WG - 1) s.bsum[(size_t)chain * s.bstride + bp.b] = loc;
-    }
+    init_weights<WG>(s, smem, bp, j, j < s.N, true, WG - 1, [&] {
+        return particle_weight<MODEL, G, OBS>(x, s.Y, cp, s.cp + chain, s.lf, s.lf_max,
+                                              s.hidden + (size_t)chain * s.hist_stride + (size_t)j * C);
+    });
 }
 
 template <int MODEL, int G, int OBS>
@@ -96,10 +87,7 @@ __global__ __launch_bounds__(64) void if2_sub_step_kernel(If2SubArgs a, int p) {
     static_assert(D <= kLaneTheta, "ChainParam::theta holds the lane's rates");
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const StepArgs& s = a.s;
-    LogTab* tab = reinterpret_cast<LogTab*>(smem);       // the layout of pf_step_kernel (step_lds_bytes)
-    double* red = smem + 2 * kLogTabEntries;
-    double* seg_start = red + 16;
-    double* seg_end = seg_start + s.nseg;
+    LogTab* tab = step_logtab(smem);
     const BlockPos bp = step_block(s);
     const int chain = bp.chain;
     const int tid = threadIdx.x;
@@ -107,46 +95,16 @@ __global__ __launch_bounds__(64) void if2_sub_step_kernel(If2SubArgs a, int p) {
     if (s.status[chain] != 0) return;
     ChainParam cp = s.cp[chain];
     cp.f += (uint32_t)a.m;
-    const int prev = (p - 1) & 1, cur = p & 1;
-    const size_t wprev = ((size_t)prev * s.max_chains + chain) * s.wstride;
-    const size_t wcur = ((size_t)cur * s.max_chains + chain) * s.wstride;
-    const size_t bprev = ((size_t)prev * s.max_chains + chain) * s.bstride;
-    const size_t bcur = ((size_t)cur * s.max_chains + chain) * s.bstride;
-
-    // likelihood of the perturbed model: zetas[p] = zetas[p-1] * mean(w), in log space (pf_step_kernel)
-    const double total = (s.seg == 1) ? scan_block_sums<WG>(s.bsum + bprev, s.B, seg_start + s.B, seg_start, red)
-                                      : scan_segments(s.bsum + bprev, s.B, s.seg, s.nseg, seg_start, seg_end);
-    if (!(total > 0.0)) {                                // all weights 0 or NaN: this search ends here
-        if (bp.b == 0 && tid == 0) {
-            s.status[chain] = kStatusDegenerate;
-            s.log_zeta[(size_t)chain * s.T + p] = -__builtin_inf();
-        }
+    const int prev = (p - 1) & 1, cur = p & 1;            // the swarm's halves, as the weights' (step_half)
+    const size_t wprev = step_half(s, chain, p - 1, s.wstride), wcur = step_half(s, chain, p, s.wstride);
+    const size_t bprev = step_half(s, chain, p - 1, s.bstride), bcur = step_half(s, chain, p, s.bstride);
+    const double total = step_total(s, smem, bprev);
+    if (!(total > 0.0)) {
+        step_degenerate(s, bp, p);
         return;
     }
-    if (bp.b == 0 && tid == 0)
-        s.log_zeta[(size_t)chain * s.T + p] = s.log_zeta[(size_t)chain * s.T + p - 1] + log(total / (double)s.N);
-
-    // multinomial draw and certified search, exactly the filter's
-    double U = 0.0;
-    int anc = 0;
-    bool certified = true, ambiguous = false;
-    if (j < s.N) {
-        const Block r = philox(0u, (uint32_t)j, ((uint32_t)p & 0xFFFFFFu) | kDomainResample, cp.f, cp.k0, cp.k1);
-        U = u01(r.x, r.y);
-        if (s.seg == 1)
-            anc = resample_search<WG>(U, seg_start + s.B, seg_start, s.B, total, s.wloc + wprev, s.N, s.cert_k,
-                                      certified, 0.0, ambiguous);
-        else
-            anc = resample_search_seg(U, seg_start, seg_end, s.nseg, s.seg, s.bsum + bprev, s.B, total,
-                                      s.wloc + wprev, WG, s.N, s.cert_k, certified, 0.0, ambiguous);
-    }
-    if (__any(!certified)) {   // wave-uniform: the whole wave resolves its uncertified draws exactly
-        const int e = resample_exact_wave(!certified, U, s.wraw + wprev, s.N);
-        if (!certified) {
-            anc = e;
-            atomicAdd(counter_slot(s.counters) + 1, 1ull);
-        }
-    }
+    step_log_zeta(s, bp, p, total);
+    int anc = step_ancestor<false>(s, smem, cp, p, j, total, wprev, bprev);
     // the ancestor's theta, jittered: this particle's rates.  The lane's own ChainParam copy differs from the chain's
     // in theta and thetaf only.  Lanes past N keep the chain's zeroed theta and run no SSA.
     double x[C];
@@ -182,24 +140,7 @@ __global__ __launch_bounds__(64) void if2_sub_step_kernel(If2SubArgs a, int p) {
         __syncthreads();
         if (!fast_ok) nev = exact_propagate<MODEL, G>(x, lcp, (uint32_t)j, ptag, 1.0, tab, iters);
     }
-    if (s.count_events) {  // pf_step_kernel's counters, before the weights so that nev and iters die here
-        unsigned long long e = (unsigned long long)nev, li = (unsigned long long)iters;
-        int wmax = iters;
-        for (int o = 32; o > 0; o >>= 1) {
-            e += __shfl_xor(e, o, 64);
-            li += __shfl_xor(li, o, 64);
-            wmax = max(wmax, __shfl_xor(wmax, o, 64));
-        }
-        const unsigned long long ex = __ballot(!fast_ok);             // lanes past N hold fast_ok = true
-        if (tid == 0) {
-            unsigned long long* slot = counter_slot(s.counters);
-            atomicAdd(slot, e);
-            atomicAdd(slot + 2, li);
-            atomicAdd(slot + 3, 64ull * (unsigned long long)wmax);
-            atomicAdd(slot + 4, (unsigned long long)__popcll(ex));    // particle-steps on the exact SSA loop
-            atomicAdd(slot + 5, ex ? 1ull : 0ull);                    // waves with at least one
-        }
-    }
+    step_count(s, nev, iters, !fast_ok);                 // lanes past N hold fast_ok = true
     double w = 0.0;
     if (j < s.N) {
         int32_t* hc = s.hidden + (size_t)chain * s.hist_stride + ((size_t)p * s.N + j) * C;
@@ -207,42 +148,29 @@ __global__ __launch_bounds__(64) void if2_sub_step_kernel(If2SubArgs a, int p) {
         for (int c = 0; c < C; ++c) hc[c] = (int32_t)x[c];
         if (p + 1 < s.T) w = particle_weight<MODEL, G, OBS>(x, s.Y + (size_t)p * K, cp, s.cp + chain, s.lf, s.lf_max, hc);
     }
-    if (p + 1 < s.T) {
-        const double loc = block_inclusive_scan<WG>(w, red);
-        s.wraw[wcur + j] = w;
-        s.wloc[wcur + j] = loc;
-        if (tid == WG - 1) s.bsum[bcur + bp.b] = loc;
-    }
+    step_store_weights(s, smem, bp.b, j, p, w, wcur, bcur);
 }
 
 template <int MODEL, int G, int OBS>
 static hipError_t launch_if2_sub_t(const If2Args& a, int n_searches, const double* half_widths, const FilterStreams& fs) {
     const StepArgs& s0 = a.s;
     const size_t lds = step_lds_bytes(s0.B, 64);
-    const int S = std::max(1, std::min(fs.n, n_searches));
-    for (int g = 0; g < S; ++g) {
+    launch_chain_groups(s0, n_searches, fs, 64, [&](int, const StepArgs& sg, int n_g, dim3 grid, hipStream_t st) {
         If2Args fin = a;                                 // if2_finish_kernel's block: the same layout and buffers
         If2SubArgs ag{};
-        ag.s = a.s; ag.d = a.d; ag.M = a.M; ag.swarm = a.swarm; ag.start = a.start;
-        ag.s.chain0 = (int)((long)n_searches * g / S);
-        const int n_g = (int)((long)n_searches * (g + 1) / S) - ag.s.chain0;
-        const hipStream_t st = fs.s[g];
-        ag.s.xcd_map = s0.xcd_map && (long)s0.B * n_g * 64 < (1L << 31);
-        const dim3 grid = ag.s.xcd_map ? dim3(s0.B * n_g) : dim3(s0.B, n_g), block(64);
+        ag.s = sg; ag.d = a.d; ag.M = a.M; ag.swarm = a.swarm; ag.start = a.start;
         for (int m = 0; m < a.M; ++m) {
             ag.m = m;
             for (int c = 0; c < a.d; ++c) ag.hw[c] = half_widths[(size_t)m * a.d + c];
             ag.s.log_zeta = s0.log_zeta + (size_t)m * s0.max_chains * s0.T;
-            hipLaunchKernelGGL((if2_sub_init_kernel<MODEL, G, OBS>), grid, block, lds, st, ag);
+            hipLaunchKernelGGL((if2_sub_init_kernel<MODEL, G, OBS>), grid, dim3(64), lds, st, ag);
             for (int p = 1; p < s0.T; ++p)
-                hipLaunchKernelGGL((if2_sub_step_kernel<MODEL, G, OBS>), grid, block, lds, st, ag, p);
+                hipLaunchKernelGGL((if2_sub_step_kernel<MODEL, G, OBS>), grid, dim3(64), lds, st, ag, p);
             fin.s = ag.s;
             fin.m = m;
             launch_if2_finish(fin, n_g, st);
         }
-        if (g > 0) (void)hipEventRecord(fs.join[g], st);
-    }
-    for (int g = 1; g < S; ++g) (void)hipStreamWaitEvent(fs.s[0], fs.join[g], 0);
+    });
     return hipGetLastError();
 }
 

@@ -1,8 +1,9 @@
 // epipf_incidence.hip -- incidence observations on MI355X (gfx950), DESIGN.md §19 (epipf_incidence.hpp).
 //
-// incidence_init_kernel / incidence_step_kernel are walk_init_kernel / walk_step_kernel (epipf_walk.hip) without the
-// per-particle parameters and with another weight: one lane per particle, one wave per block, the same block-sum
-// prefix, certified search, counters and SSA.  What is new in the step:
+// incidence_init_kernel / incidence_step_kernel filter on reported flows: one lane per particle, one wave per block, on
+// the shared phases of epipf_step.hpp (step_total, step_degenerate, step_log_zeta, step_ancestor, step_count, step_store_weights,
+// init_state, init_weights), the chain's own rates, the filter's status prologue (skipped chains) and the per-lane SSA
+// (the certified f32 loop, then the exact loop for the lanes it hands back).  Their own, in the step:
 //   - the parent state stays in registers across the propagate (int32 [C]);
 //   - the day's flows are differences of the parent and the new state (every flow of SIR / SEIR is monotone);
 //   - with CUM, a column that was not reported on day p - 1 adds the ancestor's accumulator of that day;
@@ -33,23 +34,14 @@ __global__ __launch_bounds__(64) void incidence_init_kernel(IncidenceArgs a) {
     if (j < s.N) {
         double x[C];
         init_particle<MODEL, 1>(s, cp, j, x);
-        int32_t* h = s.hidden + (size_t)chain * s.hist_stride + (size_t)j * C;
-#pragma unroll
-        for (int c = 0; c < C; ++c) h[c] = (int32_t)x[c];
-        s.ancestry[(size_t)chain * s.anc_stride + j] = 0;
+        init_state<C>(s, chain, j, x);
         if (a.acc) {                                                     // acc_0 = 0, buffer 0
 #pragma unroll
             for (int k = 0; k < F; ++k) a.acc[((size_t)chain * F + k) * s.N + j] = 0;
         }
     }
-    if (bp.b == 0 && threadIdx.x == 0) s.log_zeta[(size_t)chain * s.T] = 0.0;
     // row 0 is never reported: every particle weighs 1 (lanes past N: 0)
-    const double w = j < s.N ? 1.0 : 0.0;
-    const size_t wbase = (size_t)chain * s.wstride;                      // buffer 0
-    const double loc = block_inclusive_scan<WG>(w, smem);
-    s.wraw[wbase + j] = w;                                               // every lane: the in-block search reads the
-    s.wloc[wbase + j] = loc;                                             // whole block of the weight layout (B x 64)
-    if ((int)threadIdx.x == WG - 1) s.bsum[(size_t)chain * s.bstride + bp.b] = loc;
+    init_weights<WG>(s, smem, bp, j, j < s.N, true, WG - 1, [] { return 1.0; });
 }
 
 // One column's factor: oracle.binom_pmf(y, n, p) = exp(hi) (1 + lo) of the compensated log pmf with its special cases
@@ -75,56 +67,23 @@ __global__ __launch_bounds__(64) void incidence_step_kernel(IncidenceArgs a, int
     constexpr int WG = 64;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const StepArgs& s = a.s;
-    LogTab* tab = reinterpret_cast<LogTab*>(smem);       // the layout of pf_step_kernel (step_lds_bytes)
-    double* red = smem + 2 * kLogTabEntries;
-    double* seg_start = red + 16;
-    double* seg_end = seg_start + s.nseg;
+    LogTab* tab = step_logtab(smem);
     const BlockPos bp = step_block(s);
     const int chain = bp.chain;
     const int tid = threadIdx.x;
     const int j = bp.b * WG + tid;
     if (s.status[chain] != 0) return;
     const ChainParam cp = s.cp[chain];
-    const int prev = (p - 1) & 1, cur = p & 1;
-    const size_t wprev = ((size_t)prev * s.max_chains + chain) * s.wstride;
-    const size_t wcur = ((size_t)cur * s.max_chains + chain) * s.wstride;
-    const size_t bprev = ((size_t)prev * s.max_chains + chain) * s.bstride;
-    const size_t bcur = ((size_t)cur * s.max_chains + chain) * s.bstride;
-
-    // likelihood of the reports up to day p - 1: zetas[p] = zetas[p-1] * mean(w), in log space (pf_step_kernel)
-    const double total = (s.seg == 1) ? scan_block_sums<WG>(s.bsum + bprev, s.B, seg_start + s.B, seg_start, red)
-                                      : scan_segments(s.bsum + bprev, s.B, s.seg, s.nseg, seg_start, seg_end);
-    if (!(total > 0.0)) {                                // all weights 0 or NaN: this chain ends here
-        if (bp.b == 0 && tid == 0) {
-            s.status[chain] = kStatusDegenerate;
-            s.log_zeta[(size_t)chain * s.T + p] = -__builtin_inf();
-        }
+    const int prev = (p - 1) & 1, cur = p & 1;            // the accumulator's halves, as the weights' (step_half)
+    const size_t wprev = step_half(s, chain, p - 1, s.wstride), wcur = step_half(s, chain, p, s.wstride);
+    const size_t bprev = step_half(s, chain, p - 1, s.bstride), bcur = step_half(s, chain, p, s.bstride);
+    const double total = step_total(s, smem, bprev);
+    if (!(total > 0.0)) {
+        step_degenerate(s, bp, p);
         return;
     }
-    if (bp.b == 0 && tid == 0)
-        s.log_zeta[(size_t)chain * s.T + p] = s.log_zeta[(size_t)chain * s.T + p - 1] + log(total / (double)s.N);
-
-    // multinomial draw and certified search, exactly the filter's
-    double U = 0.0;
-    int anc = 0;
-    bool certified = true, ambiguous = false;
-    if (j < s.N) {
-        const Block r = philox(0u, (uint32_t)j, ((uint32_t)p & 0xFFFFFFu) | kDomainResample, cp.f, cp.k0, cp.k1);
-        U = u01(r.x, r.y);
-        if (s.seg == 1)
-            anc = resample_search<WG>(U, seg_start + s.B, seg_start, s.B, total, s.wloc + wprev, s.N, s.cert_k,
-                                      certified, 0.0, ambiguous);
-        else
-            anc = resample_search_seg(U, seg_start, seg_end, s.nseg, s.seg, s.bsum + bprev, s.B, total,
-                                      s.wloc + wprev, WG, s.N, s.cert_k, certified, 0.0, ambiguous);
-    }
-    if (__any(!certified)) {   // wave-uniform: the whole wave resolves its uncertified draws exactly
-        const int e = resample_exact_wave(!certified, U, s.wraw + wprev, s.N);
-        if (!certified) {
-            anc = e;
-            atomicAdd(counter_slot(s.counters) + 1, 1ull);
-        }
-    }
+    step_log_zeta(s, bp, p, total);
+    int anc = step_ancestor<false>(s, smem, cp, p, j, total, wprev, bprev);
     // the parent state: propagated in x, kept in xp for the flows
     double x[C];
     int32_t xp[C];
@@ -151,24 +110,7 @@ __global__ __launch_bounds__(64) void incidence_step_kernel(IncidenceArgs a, int
         __syncthreads();
         if (!fast_ok) nev = exact_propagate<MODEL, 1>(x, cp, (uint32_t)j, ptag, 1.0, tab, iters);
     }
-    if (s.count_events) {  // pf_step_kernel's counters
-        unsigned long long e = (unsigned long long)nev, li = (unsigned long long)iters;
-        int wmax = iters;
-        for (int o = 32; o > 0; o >>= 1) {
-            e += __shfl_xor(e, o, 64);
-            li += __shfl_xor(li, o, 64);
-            wmax = max(wmax, __shfl_xor(wmax, o, 64));
-        }
-        const unsigned long long ex = __ballot(!fast_ok);             // lanes past N hold fast_ok = true
-        if (tid == 0) {
-            unsigned long long* slot = counter_slot(s.counters);
-            atomicAdd(slot, e);
-            atomicAdd(slot + 2, li);
-            atomicAdd(slot + 3, 64ull * (unsigned long long)wmax);
-            atomicAdd(slot + 4, (unsigned long long)__popcll(ex));
-            atomicAdd(slot + 5, ex ? 1ull : 0ull);
-        }
-    }
+    step_count(s, nev, iters, !fast_ok);                 // lanes past N hold fast_ok = true
     double w = 0.0;
     if (j < s.N) {
         int32_t xn[C];
@@ -204,33 +146,21 @@ __global__ __launch_bounds__(64) void incidence_step_kernel(IncidenceArgs a, int
                     w = w * incidence_factor<OBS>(yrow[k], (double)acc[k], cp, s.lf, s.lf_max);
         }
     }
-    if (p + 1 < s.T) {
-        const double loc = block_inclusive_scan<WG>(w, red);
-        s.wraw[wcur + j] = w;                            // lanes past N: 0 and the block's sum, in the weight layout's
-        s.wloc[wcur + j] = loc;                          // own padding (B x 64 slots); they touch no particle array
-        if (tid == WG - 1) s.bsum[bcur + bp.b] = loc;
-    }
+    step_store_weights(s, smem, bp.b, j, p, w, wcur, bcur);
 }
 
 template <int MODEL, int OBS, bool CUM>
 static hipError_t launch_incidence_t(const IncidenceArgs& a, const uint8_t* rep, int n_chains, const FilterStreams& fs) {
     const StepArgs& s0 = a.s;
     const size_t lds = step_lds_bytes(s0.B, 64);
-    const int S = std::max(1, std::min(fs.n, n_chains));
-    for (int g = 0; g < S; ++g) {
+    launch_chain_groups(s0, n_chains, fs, 64, [&](int, const StepArgs& sg, int, dim3 grid, hipStream_t st) {
         IncidenceArgs ag = a;
-        ag.s.chain0 = (int)((long)n_chains * g / S);
-        const int n_g = (int)((long)n_chains * (g + 1) / S) - ag.s.chain0;
-        const hipStream_t st = fs.s[g];
-        ag.s.xcd_map = s0.xcd_map && (long)s0.B * n_g * 64 < (1L << 31);
-        const dim3 grid = ag.s.xcd_map ? dim3(s0.B * n_g) : dim3(s0.B, n_g), block(64);
-        hipLaunchKernelGGL((incidence_init_kernel<MODEL>), grid, block, lds, st, ag);
+        ag.s = sg;
+        hipLaunchKernelGGL((incidence_init_kernel<MODEL>), grid, dim3(64), lds, st, ag);
         for (int p = 1; p < s0.T; ++p)
-            hipLaunchKernelGGL((incidence_step_kernel<MODEL, OBS, CUM>), grid, block, lds, st, ag, p, (int)rep[p - 1],
+            hipLaunchKernelGGL((incidence_step_kernel<MODEL, OBS, CUM>), grid, dim3(64), lds, st, ag, p, (int)rep[p - 1],
                                (int)rep[p]);
-        if (g > 0) (void)hipEventRecord(fs.join[g], st);
-    }
-    for (int g = 1; g < S; ++g) (void)hipStreamWaitEvent(fs.s[0], fs.join[g], 0);
+    });
     return hipGetLastError();
 }
 

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "epipf_device.hpp"
 
 // roctx ranges (the debug build, EPIPF_ROCTX): one around each epipf_run (an MH iteration's filter) and one around
@@ -239,6 +241,25 @@ struct FilterStreams {
     hipEvent_t ev_init, ev_step0, ev_end;   // timing (profiling on) or null
     hipEvent_t g_begin[kMaxFilterStreams], g_end[kMaxFilterStreams];   // per-group step-kernel span, or null
 };
+
+// The launch loop of every one-lane-per-particle filter.  Chains are independent, so chain groups advance through
+// their steps on separate streams: one group's end-of-launch tail (the last, partial round of waves) overlaps the other
+// groups' launches.  The n chains are dealt over min(fs.n, n) groups; run(g, sg, n_g, grid, stream) enqueues group g's
+// kernels with its copy sg of the arguments (chain0, and xcd_map: the 1-D XCD-aware grid while its work-items -- B x
+// n_g blocks of block_threads -- fit HIP's 32-bit x extent, else the 2-D grid).  Then fs.s[0] waits for the others.
+template <class Run>
+static void launch_chain_groups(const StepArgs& a, int n, const FilterStreams& fs, int block_threads, Run&& run) {
+    const int S = std::max(1, std::min(fs.n, n));
+    for (int g = 0; g < S; ++g) {
+        StepArgs sg = a;
+        sg.chain0 = (int)((long)n * g / S);
+        const int n_g = (int)((long)n * (g + 1) / S) - sg.chain0;
+        sg.xcd_map = a.xcd_map && (long)a.B * n_g * block_threads < (1L << 31);
+        run(g, sg, n_g, sg.xcd_map ? dim3(a.B * n_g) : dim3(a.B, n_g), fs.s[g]);
+        if (g > 0) (void)hipEventRecord(fs.join[g], fs.s[g]);
+    }
+    for (int g = 1; g < S; ++g) (void)hipStreamWaitEvent(fs.s[0], fs.join[g], 0);
+}
 
 // logfact.cpp (host, binary128): log n! and log p / log1p(-p) split into hi + lo doubles
 void logfact_table(int n_max, double* out);

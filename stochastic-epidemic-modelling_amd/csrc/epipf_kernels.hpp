@@ -1,6 +1,10 @@
 // epipf_kernels.hpp -- the one-lane-per-particle kernel templates (init, filter step, simulate, simulate_path) and
 // their launch helpers, shared by the translation units that instantiate them: epipf_kernels.hip (SIR, SEIR and the
 // subgroup models up to G = 4) and epipf_kernels_wide.hip (the subgroup models at G = 5..8, split off for compile time).
+// pf_init_kernel / pf_step_kernel run the shared phases of epipf_step.hpp; their own are the skip
+// status, the blocks of fewer than WG particles (lane-group layouts), the systematic draw and the ambiguity count
+// (step_ancestor<true>), the chain's wave-uniform rates and the cooperative replay of the lanes the f32 loop hands back.
+// pf_step_kernel keeps one shared phase inline, the block-sum scan (step_total's body).
 #pragma once
 #include "epipf_step.hpp"
 #include <algorithm>
@@ -38,25 +42,12 @@ __global__ __launch_bounds__(WG) void pf_init_kernel(StepArgs a) {
             init_particle_wide<MODEL, G>(a, cp, j, x, wide_param(a.cp, a.max_chains, chain));
         else
             init_particle<MODEL, G>(a, cp, j, x);
-        int32_t* h = a.hidden + (size_t)chain * a.hist_stride + (size_t)j * C;
-#pragma unroll
-        for (int c = 0; c < C; ++c) h[c] = (int32_t)x[c];
-        a.ancestry[(size_t)chain * a.anc_stride + j] = 0;
+        init_state<C>(a, chain, j, x);
     }
-    if (bp.b == 0 && threadIdx.x == 0) a.log_zeta[(size_t)chain * a.T] = 0.0;
-    if (a.T > 1) {
-        double w = 0.0;
-        if (mine && j < a.N)
-            w = particle_weight<MODEL, G, OBS>(x, a.Y, cp, a.cp + chain, a.lf, a.lf_max,
-                                               a.hidden + (size_t)chain * a.hist_stride + (size_t)j * C);
-        const size_t wbase = (size_t)chain * a.wstride;            // buffer 0
-        const double loc = block_inclusive_scan<WG>(w, smem);
-        if (mine) {
-            a.wraw[wbase + j] = w;
-            a.wloc[wbase + j] = loc;
-        }
-        if ((int)threadIdx.x == a.wg - 1) a.bsum[(size_t)chain * a.bstride + bp.b] = loc;
-    }
+    init_weights<WG>(a, smem, bp, j, mine && j < a.N, mine, a.wg - 1, [&] {
+        return particle_weight<MODEL, G, OBS>(x, a.Y, cp, a.cp + chain, a.lf, a.lf_max,
+                                              a.hidden + (size_t)chain * a.hist_stride + (size_t)j * C);
+    });
 }
 
 template <int MODEL, int G, int OBS, int WG>
@@ -65,68 +56,33 @@ __global__ __launch_bounds__(WG, EPIPF_STEP_WAVES) void pf_step_kernel(StepArgs 
     constexpr int C = Sh::C;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     static_assert(WG == 64, "one wave per block (scan_segments)");
-    LogTab* tab = reinterpret_cast<LogTab*>(smem);       // 128 x 16 B log table (first: 16-B aligned)
-    double* red = smem + 2 * kLogTabEntries;             // WG/64 (+pad)
-    double* seg_start = red + 16;                        // S = 1: bsum [B] then bpex [B + WG]; else nseg + nseg
-    double* seg_end = seg_start + a.nseg;
+    LogTab* tab = step_logtab(smem);
+    double* red = step_red(smem);                        // for the block-sum scan below, step_total's body: it stays
+    double* seg_start = step_prefix(smem);               // inline in this kernel, with its pointers taken here, because
+    double* seg_end = seg_start + a.nseg;                // as a call every instance's generated code moved
     const BlockPos bp = step_block(a);
     const int chain = bp.chain;
     const int tid = threadIdx.x;
     const int j = bp.b * WG + tid;
     if (a.status[chain] != 0) return;
     const ChainParam cp = a.cp[chain];
-    const int prev = (p - 1) & 1, cur = p & 1;
-    const size_t wprev = ((size_t)prev * a.max_chains + chain) * a.wstride;
-    const size_t wcur = ((size_t)cur * a.max_chains + chain) * a.wstride;
-    const size_t bprev = ((size_t)prev * a.max_chains + chain) * a.bstride;
-    const size_t bcur = ((size_t)cur * a.max_chains + chain) * a.bstride;
+    const size_t wprev = step_half(a, chain, p - 1, a.wstride), wcur = step_half(a, chain, p, a.wstride);
+    const size_t bprev = step_half(a, chain, p - 1, a.bstride), bcur = step_half(a, chain, p, a.bstride);
 
     // (b) likelihood: zetas[p] = zetas[p-1] * mean(w)  (pmcmc.py:183), kept in log space
     // S = 1 (B <= kMaxSegments): the block sums and their exclusive prefix stay in LDS; else segment ends only
     const double total = (a.seg == 1) ? scan_block_sums<WG>(a.bsum + bprev, a.B, seg_start + a.B, seg_start, red)
                                       : scan_segments(a.bsum + bprev, a.B, a.seg, a.nseg, seg_start, seg_end);
     if (!(total > 0.0)) {  // all weights 0 or NaN: numpy raises ValueError -> (None, None, None), :187-192
-        if (bp.b == 0 && tid == 0) {
-            a.status[chain] = 1;
-            a.log_zeta[(size_t)chain * a.T + p] = -__builtin_inf();
-        }
+        step_degenerate(a, bp, p);
         return;
     }
-    if (bp.b == 0 && tid == 0)
-        a.log_zeta[(size_t)chain * a.T + p] = a.log_zeta[(size_t)chain * a.T + p - 1] + log(total / (double)a.N);
+    step_log_zeta(a, bp, p, total);
 
-    int nev = 0, iters = 0, exact = 0;
+    int nev = 0, iters = 0;
     double w = 0.0;
-    // (d) multinomial (or systematic) draw and certified search, pmcmc.py:188-190
-    double U = 0.0;
-    int anc = 0;
-    bool certified = true, ambiguous = false;
-    if (j < a.N) {
-        const uint32_t rtag = ((uint32_t)p & 0xFFFFFFu) | kDomainResample;
-        if (a.resample_mode == 0) {
-            const Block r = philox(0u, (uint32_t)j, rtag, cp.f, cp.k0, cp.k1);
-            U = u01(r.x, r.y);
-        } else {
-            const Block r = philox(0u, 0u, rtag, cp.f, cp.k0, cp.k1);
-            U = ((double)j + u01(r.x, r.y)) / (double)a.N;
-        }
-        if (a.seg == 1)
-            anc = resample_search<WG>(U, seg_start + a.B, seg_start, a.B, total, a.wloc + wprev, a.N, a.cert_k,
-                                      certified, a.ref_k, ambiguous);
-        else
-            anc = resample_search_seg(U, seg_start, seg_end, a.nseg, a.seg, a.bsum + bprev, a.B, total,
-                                      a.wloc + wprev, WG, a.N, a.cert_k, certified, a.ref_k, ambiguous);
-    }
-    // reference-ambiguous draws (rare: ~1e-8 of draws at config 2; every uncertified one included), counted with
-    // the other device counters (EPIPF_PROFILE_COUNTERS: bench.py's untimed counters iteration, the parity tests)
-    if (ambiguous) atomicAdd(counter_slot(a.counters) + 6, 1ull);
-    if (__any(!certified)) {   // wave-uniform: the whole wave resolves its uncertified draws exactly
-        const int e = resample_exact_wave(!certified, U, a.wraw + wprev, a.N);
-        if (!certified) {
-            anc = e;
-            atomicAdd(counter_slot(a.counters) + 1, 1ull);
-        }
-    }
+    // (d) the draw (multinomial or systematic), the certified search, the ambiguity count, pmcmc.py:188-190
+    int anc = step_ancestor<true>(a, smem, cp, p, j, total, wprev, bprev);
     // (f) gather the parent state, (g) propagate over [0, 1], :195-220: the certified f32 loop, then the exact path
     // for the lanes it hands back.  The exact path's log table is copied to LDS only by waves that need it (~1% at
     // config 2): one wave per block, so the wave-uniform test is block-uniform and the barriers are legal.
@@ -145,8 +101,8 @@ __global__ __launch_bounds__(WG, EPIPF_STEP_WAVES) void pf_step_kernel(StepArgs 
         for (int c = 0; c < C; ++c) x[c] = (double)hp[c];
         fast_ok = fast_propagate<MODEL, G>(x, cp, (uint32_t)j, ptag, 1.0, nev, iters, eligible, wp);
     }
-    exact = (j < a.N && !fast_ok) ? 1 : 0;
-    if (__any(exact != 0)) {
+    const bool exact = j < a.N && !fast_ok;
+    if (__any(exact)) {
         for (int i = tid; i < kLogTabEntries; i += WG) tab[i] = a.logtab[i];
         __syncthreads();
         // lanes the f32 loop could not run (population or rates out of its range): the exact loop, per lane
@@ -157,7 +113,7 @@ __global__ __launch_bounds__(WG, EPIPF_STEP_WAVES) void pf_step_kernel(StepArgs 
         }
         // lanes it stopped at the step boundary: replayed one at a time by the whole wave (coop_replay).  The lanes'
         // states wait in their output rows meanwhile (x is not live across the replay: registers, occupancy).
-        unsigned long long pend = __ballot(exact != 0 && eligible);
+        unsigned long long pend = __ballot(exact && eligible);
         if (pend) {
             int32_t* hrow = a.hidden + (size_t)chain * a.hist_stride + (size_t)p * a.N * C;
             if (j < a.N) {
@@ -186,30 +142,8 @@ __global__ __launch_bounds__(WG, EPIPF_STEP_WAVES) void pf_step_kernel(StepArgs 
         // (a) weights of the new state against Y[p], used by step p+1, :178-181
         if (p + 1 < a.T) w = particle_weight<MODEL, G, OBS>(x, a.Y + (size_t)p * Sh::K, cp, a.cp + chain, a.lf, a.lf_max, hc);
     }
-    if (a.count_events) {  // accepted events; lane-iterations; wave-iterations x 64 (lane utilisation)
-        unsigned long long e = (unsigned long long)nev, li = (unsigned long long)iters;
-        int wmax = iters;
-        for (int o = 32; o > 0; o >>= 1) {
-            e += __shfl_xor(e, o, 64);
-            li += __shfl_xor(li, o, 64);
-            wmax = max(wmax, __shfl_xor(wmax, o, 64));
-        }
-        const unsigned long long ex = __ballot(exact != 0);
-        if ((tid & 63) == 0) {
-            unsigned long long* slot = counter_slot(a.counters);
-            atomicAdd(slot, e);
-            atomicAdd(slot + 2, li);
-            atomicAdd(slot + 3, 64ull * (unsigned long long)wmax);
-            atomicAdd(slot + 4, (unsigned long long)__popcll(ex));        // lanes on the exact SSA loop
-            atomicAdd(slot + 5, ex ? 1ull : 0ull);                        // waves with at least one
-        }
-    }
-    if (p + 1 < a.T) {
-        const double loc = block_inclusive_scan<WG>(w, red);
-        a.wraw[wcur + j] = w;
-        a.wloc[wcur + j] = loc;
-        if (tid == WG - 1) a.bsum[bcur + bp.b] = loc;
-    }
+    step_count(a, nev, iters, exact);
+    step_store_weights(a, smem, bp.b, j, p, w, wcur, bcur);
 }
 
 template <int MODEL, int G>
@@ -285,24 +219,16 @@ __global__ __launch_bounds__(256) void simulate_path_kernel(SimPathArgs a) {
 template <int MODEL, int G, int OBS, int WG>
 static hipError_t launch_filter_t(const StepArgs& a, int n_chains, const FilterStreams& fs) {
     constexpr int C = Shape<MODEL, G>::C;
-    // Chains are independent, so chain groups advance through their T steps on separate streams: one group's
-    // end-of-launch tail (the last, partial round of waves) overlaps the other groups' launches.
     const size_t lds = step_lds_bytes(a.B, WG);
-    const int S = std::max(1, std::min(fs.n, n_chains));
     // W lanes per particle (runs too small to fill the chip): the lane-group step kernel, epipf_group.hip
     const GroupStepFn group = a.lanes > 1 ? group_step_launcher(MODEL, G, OBS, a.lanes, a.lane_events) : nullptr;
     if (a.lanes > 1 && !group) return hipErrorInvalidValue;
     const size_t glds = group ? group_lds_bytes(a.B, a.seg, C, a.lanes, a.lane_events, a.wg) : 0;
-    for (int g = 0; g < S; ++g) {
-        StepArgs ag = a;
-        ag.chain0 = (int)((long)n_chains * g / S);
-        const int n_g = (int)((long)n_chains * (g + 1) / S) - ag.chain0;
-        const hipStream_t s = fs.s[g];
-        // the 1-D XCD-aware grid while its work-items fit HIP's 32-bit x extent (with room for lane-group blocks)
-        ag.xcd_map = a.xcd_map && (long)a.B * n_g * WG * std::max(1, a.lanes) < (1L << 31);
-        const dim3 grid = ag.xcd_map ? dim3(a.B * n_g) : dim3(a.B, n_g), block(WG);
+    // the grid-size test leaves room for the lane-group blocks
+    launch_chain_groups(a, n_chains, fs, WG * std::max(1, a.lanes),
+                        [&](int g, const StepArgs& ag, int, dim3 grid, hipStream_t s) {
         if (g == 0 && fs.ev_init) (void)hipEventRecord(fs.ev_init, s);
-        hipLaunchKernelGGL((pf_init_kernel<MODEL, G, OBS, WG>), grid, block, lds, s, ag);
+        hipLaunchKernelGGL((pf_init_kernel<MODEL, G, OBS, WG>), grid, dim3(WG), lds, s, ag);
         if (g == 0 && fs.ev_step0) (void)hipEventRecord(fs.ev_step0, s);
         if (fs.g_begin[g]) (void)hipEventRecord(fs.g_begin[g], s);
         for (int p = 1; p < a.T; ++p) {
@@ -312,13 +238,11 @@ static hipError_t launch_filter_t(const StepArgs& a, int n_chains, const FilterS
             EPIPF_RANGE_PUSH(msg);
 #endif
             if (group) group(ag, p, grid, glds, s);
-            else hipLaunchKernelGGL((pf_step_kernel<MODEL, G, OBS, WG>), grid, block, lds, s, ag, p);
+            else hipLaunchKernelGGL((pf_step_kernel<MODEL, G, OBS, WG>), grid, dim3(WG), lds, s, ag, p);
             EPIPF_RANGE_POP();
         }
         if (fs.g_end[g]) (void)hipEventRecord(fs.g_end[g], s);
-        if (g > 0) (void)hipEventRecord(fs.join[g], s);
-    }
-    for (int g = 1; g < S; ++g) (void)hipStreamWaitEvent(fs.s[0], fs.join[g], 0);
+    });
     if (fs.ev_end) (void)hipEventRecord(fs.ev_end, fs.s[0]);
     return hipGetLastError();
 }

@@ -1,5 +1,8 @@
-// epipf_step.hpp -- the block-sum prefix helpers shared by the one-lane-per-particle step kernel
-// (epipf_kernels.hip) and the lane-group step kernel (epipf_group.hip).
+// epipf_step.hpp -- what the filter kernels share: the grid mapping (step_block), the initial state (init_particle),
+// the block-sum prefix scans, also used by the lane-group step kernel (epipf_group.hip), and the phases of a
+// one-lane-per-particle step and init kernel (step_half .. init_weights), which the plain filter
+// (epipf_kernels.hpp), IF2 (epipf_if2.hip, epipf_if2_sub.hip), the random-walk filter (epipf_walk.hip) and the
+// incidence filter (epipf_incidence.hip) call around their own middle.
 #pragma once
 #include "epipf_device.hpp"
 #include "epipf_internal.hpp"
@@ -189,6 +192,159 @@ __device__ __forceinline__ double scan_block_sums16(const double* __restrict__ b
     }
     lds_sync<WAVE>();
     return *tot;
+}
+
+// ------------------------------------------------------------------ the phases of a one-lane-per-particle step
+// One lane per particle, one wave per block (64 threads), the weight layout of 64-particle blocks: the plain filter
+// (pf_step_kernel), IF2 (epipf_if2.hip, epipf_if2_sub.hip), the random-walk filter (epipf_walk.hip) and the incidence
+// filter (epipf_incidence.hip) run these phases around their own middle.  Every helper takes the
+// kernel's dynamic LDS (step_lds_bytes) and carves it up itself,
+//   LogTab tab[kLogTabEntries] | double red[16] | S = 1: bsum [B], bpex [B + 64]; else seg_start [nseg], seg_end [nseg]
+// because pointers handed on in a struct lose the LDS address space (generic loads in place of ds_read).
+__device__ __forceinline__ LogTab* step_logtab(double* smem) { return reinterpret_cast<LogTab*>(smem); }
+__device__ __forceinline__ double* step_red(double* smem) { return smem + 2 * kLogTabEntries; }
+__device__ __forceinline__ double* step_prefix(double* smem) { return smem + 2 * kLogTabEntries + 16; }
+
+// Offset of a chain's slice in the half of step q of a double buffer with `stride` elements per chain: step p reads
+// what step p - 1 wrote (q = p - 1: wraw, wloc and bsum) and writes the half of q = p.  A function of scalars, not a
+// struct of the four offsets: the struct costs step kernel instances scalar spills.
+__device__ __forceinline__ size_t step_half(const StepArgs& a, int chain, int q, size_t stride) {
+    return ((size_t)(q & 1) * a.max_chains + chain) * stride;
+}
+
+// (b) likelihood: zetas[p] = zetas[p-1] * mean(w) (pmcmc.py:183), kept in log space.  step_total: the prefix of the
+// previous step's block sums into LDS -- S = 1 (B <= kMaxSegments): the block sums and their exclusive prefix; else the
+// segment ends only -- and their total.  A kernel then branches on the total itself,
+//     if (!(total > 0.0)) { step_degenerate(a, bp, p); return; }
+//     step_log_zeta(a, bp, p, total);
+// all weights 0 or NaN (numpy raises ValueError -> (None, None, None), :187-192): the chain ends here, degenerate, and
+// the block returns; else log_zeta[p].  The branch stays in the kernel and the helpers take and return values only
+// (an exit inside a helper, or an output reference, costs the kernels scalar spills).
+// pf_step_kernel (epipf_kernels.hpp) carries a copy of this body inline: a change to the segment layout goes in both.
+__device__ __forceinline__ double step_total(const StepArgs& a, double* smem, size_t bprev) {
+    double* red = step_red(smem);
+    double* seg_start = step_prefix(smem);
+    double* seg_end = seg_start + a.nseg;
+    const double total = (a.seg == 1) ? scan_block_sums<64>(a.bsum + bprev, a.B, seg_start + a.B, seg_start, red)
+                                      : scan_segments(a.bsum + bprev, a.B, a.seg, a.nseg, seg_start, seg_end);
+    return total;
+}
+__device__ __forceinline__ void step_degenerate(const StepArgs& a, const BlockPos& bp, int p) {
+    if (bp.b == 0 && threadIdx.x == 0) {
+        a.status[bp.chain] = kStatusDegenerate;
+        a.log_zeta[(size_t)bp.chain * a.T + p] = -__builtin_inf();
+    }
+}
+__device__ __forceinline__ void step_log_zeta(const StepArgs& a, const BlockPos& bp, int p, double total) {
+    if (bp.b == 0 && threadIdx.x == 0)
+        a.log_zeta[(size_t)bp.chain * a.T + p] = a.log_zeta[(size_t)bp.chain * a.T + p - 1] + log(total / (double)a.N);
+}
+
+// (d) particle j's ancestor: the multinomial draw on (0, j, p | resample, f), the certified two-level search of the
+// prefix step_total left in LDS, and for the draws it could not certify the exact search by the whole wave, counted in
+// slot 1 (pmcmc.py:188-190).  The caller clamps the result (checked_index).  REF, the plain filter alone: the
+// systematic draw (a.resample_mode), and with a.ref_k > 0 the reference-ambiguous draws counted in slot 6 (rare: ~1e-8
+// of draws at config 2; every uncertified one included).  Without REF neither costs a branch or a register.
+template <bool REF>
+__device__ __forceinline__ int step_ancestor(const StepArgs& a, double* smem, const ChainParam& cp, int p, int j,
+                                             double total, size_t wprev, size_t bprev) {
+    double* seg_start = step_prefix(smem);
+    double U = 0.0;
+    int anc = 0;
+    bool certified = true, ambiguous = false;
+    if (j < a.N) {
+        const uint32_t rtag = ((uint32_t)p & 0xFFFFFFu) | kDomainResample;
+        if (!REF || a.resample_mode == 0) {
+            const Block r = philox(0u, (uint32_t)j, rtag, cp.f, cp.k0, cp.k1);
+            U = u01(r.x, r.y);
+        } else {
+            const Block r = philox(0u, 0u, rtag, cp.f, cp.k0, cp.k1);
+            U = ((double)j + u01(r.x, r.y)) / (double)a.N;
+        }
+        const double ref_k = REF ? a.ref_k : 0.0;
+        if (a.seg == 1)
+            anc = resample_search<64>(U, seg_start + a.B, seg_start, a.B, total, a.wloc + wprev, a.N, a.cert_k,
+                                      certified, ref_k, ambiguous);
+        else
+            anc = resample_search_seg(U, seg_start, seg_start + a.nseg, a.nseg, a.seg, a.bsum + bprev, a.B, total,
+                                      a.wloc + wprev, 64, a.N, a.cert_k, certified, ref_k, ambiguous);
+    }
+    if constexpr (REF) {
+        if (ambiguous) atomicAdd(counter_slot(a.counters) + 6, 1ull);
+    }
+    if (__any(!certified)) {   // wave-uniform: the whole wave resolves its uncertified draws exactly
+        const int e = resample_exact_wave(!certified, U, a.wraw + wprev, a.N);
+        if (!certified) {
+            anc = e;
+            atomicAdd(counter_slot(a.counters) + 1, 1ull);
+        }
+    }
+    return anc;
+}
+
+// The event counters of a wave (a.count_events: EPIPF_PROFILE_COUNTERS): accepted events, lane-iterations,
+// wave-iterations x 64 (lane utilisation), and from `exact` -- the lane left the certified f32 loop for the exact SSA
+// loop; false in lanes past N -- the particle-steps on the exact loop and the waves with at least one.
+__device__ __forceinline__ void step_count(const StepArgs& a, int nev, int iters, bool exact) {
+    if (!a.count_events) return;
+    unsigned long long e = (unsigned long long)nev, li = (unsigned long long)iters;
+    int wmax = iters;
+    for (int o = 32; o > 0; o >>= 1) {
+        e += __shfl_xor(e, o, 64);
+        li += __shfl_xor(li, o, 64);
+        wmax = max(wmax, __shfl_xor(wmax, o, 64));
+    }
+    const unsigned long long ex = __ballot(exact);
+    if (threadIdx.x == 0) {
+        unsigned long long* slot = counter_slot(a.counters);
+        atomicAdd(slot, e);
+        atomicAdd(slot + 2, li);
+        atomicAdd(slot + 3, 64ull * (unsigned long long)wmax);
+        atomicAdd(slot + 4, (unsigned long long)__popcll(ex));
+        atomicAdd(slot + 5, ex ? 1ull : 0ull);
+    }
+}
+
+// The weights step p + 1 reads: w (0 in lanes past N), the block's inclusive prefix and its sum, in the weight
+// layout's own padding (B x 64 slots), so every lane stores.  The last step is followed by none and stores nothing.
+__device__ __forceinline__ void step_store_weights(const StepArgs& a, double* smem, int b, int j, int p, double w,
+                                                   size_t wcur, size_t bcur) {
+    if (p + 1 >= a.T) return;
+    const double loc = block_inclusive_scan<64>(w, step_red(smem));
+    a.wraw[wcur + j] = w;
+    a.wloc[wcur + j] = loc;
+    if (threadIdx.x == 63) a.bsum[bcur + b] = loc;
+}
+
+// The two shared ends of an init kernel.  init_state: particle j's state x into row 0 of the history and its ancestor
+// 0.  init_weights: log_zeta[0] = 0, and with a step to follow (T > 1; the incidence filter's T >= 3 always) the weights
+// of row 0 into half 0 of the weight buffers with the block's scan.  weight() is the kernel's own, called in the lanes
+// that hold a particle (`live`; the others weigh 0) after the state is stored: the binomial weight's tie path reads the
+// row back.  smem: the kernel's dynamic LDS, as in the step helpers; an init kernel scans in its first doubles.
+// `mine`: the lane holds a slot of the weight layout, `last`: the lane of the block's last slot (blocks of fewer than
+// WG particles in the lane-group runs' layout: the lanes past a.wg store nothing).
+template <int C>
+__device__ __forceinline__ void init_state(const StepArgs& a, int chain, int j, const double* x) {
+    int32_t* h = a.hidden + (size_t)chain * a.hist_stride + (size_t)j * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c) h[c] = (int32_t)x[c];
+    a.ancestry[(size_t)chain * a.anc_stride + j] = 0;
+}
+template <int WG, class Weight>
+__device__ __forceinline__ void init_weights(const StepArgs& a, double* smem, const BlockPos& bp, int j, bool live,
+                                             bool mine, int last, Weight weight) {
+    if (bp.b == 0 && threadIdx.x == 0) a.log_zeta[(size_t)bp.chain * a.T] = 0.0;
+    if (a.T > 1) {
+        double w = 0.0;
+        if (live) w = weight();
+        const size_t wbase = (size_t)bp.chain * a.wstride;            // buffer 0
+        const double loc = block_inclusive_scan<WG>(w, smem);
+        if (mine) {
+            a.wraw[wbase + j] = w;
+            a.wloc[wbase + j] = loc;
+        }
+        if ((int)threadIdx.x == last) a.bsum[(size_t)bp.chain * a.bstride + bp.b] = loc;
+    }
 }
 
 }  // namespace epipf
