@@ -38,6 +38,8 @@
  *                        parameters kept, and smoothed daily beta, gamma and R_t as mean and quantiles
  *   epipf_run_incidence  no reference counterpart: the filter on reported case counts (new infections, onsets, removals
  *                        per day, with gaps and cumulated reports) instead of the compartments themselves
+ *   epipf_incidence_walk / epipf_incidence_smooth   no reference counterpart: R_t from case counts -- the random-walk
+ *                        filter weighted by those reports, and the smoothed true flows per day of an incidence pass
  *
  * The host wrapper (stochastic-epidemic-modelling_amd/epipf/) binds these with ctypes and keeps
  * the reference's Python signatures.  Conventions:
@@ -432,6 +434,35 @@ int epipf_walk_smooth_history(epipf_ctx* ctx, int n, int T, int N, int C, int d,
 int epipf_run_incidence(epipf_ctx* ctx, int n_chains, const double* theta, int d, int obs_model, const double* probs,
                         const uint64_t* keys, const uint32_t* filter_index, const int32_t* active, const double* counts,
                         int D, int cumulate, double* log_zetas_out, int32_t* status_out);
+
+/* R_t from case counts for the SIR and SEIR models: the random-walk filter of epipf_walk_filter weighted
+ * by the reports of epipf_run_incidence.  Every particle carries its own theta, jittered at every step by the
+ * half-widths of its chain (the same perturb, Philox domain 7 << 24; no new domain, counter layout or stream), over the
+ * T = D + 2 rows of the incidence pass, with its flows, accumulator and product weight as defined above.
+ *   swarm_in [n_chains*N*d], half_widths [n_chains*d]: epipf_walk_filter's rules;  probs, keys, filter_index [n_chains]
+ *   counts [D*F], D, cumulate, probs: epipf_run_incidence's rules and error texts (every chain runs: no `active`)
+ *   log_zetas_out [n_chains*(D+2)];  status_out [n_chains]
+ * theta_hist is kept over the D + 2 rows and the run length becomes D + 2: epipf_walk_history, epipf_walk_smooth,
+ * epipf_copy_history, epipf_path_sample, epipf_smooth, epipf_smooth_lag and epipf_incidence_smooth see the pass
+ * afterwards.  A chain that degenerates at step p has log_zetas -inf from row p on and NaN theta rows from p on.
+ * EPIPF_EINVAL on a subgroup context; EPIPF_ESTATE without epipf_set_population (observations are not needed);
+ * EPIPF_ENOMEM as epipf_walk_filter (theta_hist) and epipf_run_incidence (the accumulator and its budget). */
+int epipf_incidence_walk(epipf_ctx* ctx, int n_chains, const double* swarm_in, int d, const double* half_widths,
+                         int obs_model, const double* probs, const uint64_t* keys, const uint32_t* filter_index,
+                         const double* counts, int D, int cumulate, double* log_zetas_out, int32_t* status_out);
+
+/* The smoothed true flows of the last epipf_run_incidence or epipf_incidence_walk (EPIPF_ESTATE before one, and after
+ * any other run has overwritten the context's history).  With T = D + 2 and F the model's flow columns,
+ *   flow[p][i][k] = the flows of epipf_run_incidence between hidden[p-1][ancestry[p][i]] and hidden[p][i] for p >= 1,
+ *                   0 in row 0: the day's own flow, also under cumulate
+ * formed on the device and reduced as epipf_smooth_lag reduces a history of F compartments, under the multiplicities of
+ * EPIPF_LINEAGE_GENEALOGY (the flows are defined by the true parent) at `lag` (lag < 0 or lag >= T-1: the full
+ * smoother; 0: the particle cloud):
+ *   sums_out [n*T*F];  quant_out [n*n_q*T*F] (NULL with n_q = 0);  lineages_out [n*T]
+ * The quantile rule, bins (a flow is at most the population total), slicing and the zeros of chains that are not
+ * EPIPF_STATUS_OK are epipf_smooth_lag's. */
+int epipf_incidence_smooth(epipf_ctx* ctx, int n_chains, int lag, const double* q, int n_q, int bins, int64_t* sums_out,
+                           int32_t* quant_out, int32_t* lineages_out);
 
 /* The device's restatement of glibc's log (the reference's math.log / numpy legacy exponential),
  * evaluated on the host CPU with the same code and table: out[i] = log(x[i]) bit for bit for normal x[i] > 0.

@@ -27,6 +27,7 @@
 #include "epipf_smooth.hpp"
 #include "epipf_smooth_lag.hpp"
 #include "epipf_walk.hpp"
+#include "epipf_walk_incidence.hpp"
 
 using namespace epipf;
 
@@ -151,6 +152,9 @@ struct epipf_ctx {
     size_t inc_counts_n = 0;
     int32_t* inc_acc = nullptr;
     size_t inc_acc_bytes = 0, inc_acc_limit = 0;
+    // while the context's history is an incidence pass's (epipf_run_incidence, epipf_incidence_walk): what
+    // epipf_incidence_smooth reduces
+    bool inc_valid = false;
 };
 
 // Lanes per particle for a run of n_chains filters.  The one-lane kernel needs ~20k waves per launch to fill the
@@ -704,6 +708,7 @@ static int run_impl(epipf_ctx* c, int n_chains, const double* theta, int d, int 
     }
     HIP_TRY(hipSetDevice(c->device));
     c->walk_valid = false;                               // the history is this run's from here on
+    c->inc_valid = false;
     HIP_TRY(hipMemcpyAsync(c->cp, c->h_cp, sizeof(ChainParam) * n_chains, hipMemcpyHostToDevice, c->stream));
     if (c->G > kMaxLaneG)   // the chains' WideParam blocks, behind the ChainParam array on both sides
         HIP_TRY(hipMemcpyAsync(const_cast<WideParam*>(wide_param(c->cp, c->max_chains, 0)), wide_param(c->h_cp, c->max_chains, 0),
@@ -1227,12 +1232,13 @@ constexpr size_t kSmoothScratch = (size_t)4 << 30;
 constexpr int kSmoothNoLag = -1;
 
 // The smoother over n chains of [T][N][C] histories: the context's own (up_hidden == NULL: its strides and the last
-// run's status) or the caller's host arrays, uploaded to scratch.  lag >= 0 is the fixed-lag pass (§16.1, `kind` is
+// run's status), the caller's host arrays, uploaded to scratch, or (flows: up_hidden == NULL, C = F) the true flows of
+// the context's own history, formed on the device into scratch with its ancestry and status.  lag >= 0 is the fixed-lag pass (§16.1, `kind` is
 // EPIPF_SMOOTH_SMOOTHING): one workgroup per (chain, day), the days of a chain sliced too when its global rows alone
 // exceed the budget; lag >= T - 1 is the smoother itself and runs as it.
 static int smooth_run(epipf_ctx* c, int n, int T, int N, int C, const int32_t* up_hidden, const int32_t* up_ancestry,
                       int lineage, int kind, int lag, const double* q, int n_q, int bins, int64_t* sums_out,
-                      int32_t* quant_out, int32_t* lineages_out) {
+                      int32_t* quant_out, int32_t* lineages_out, bool flows = false) {
     if (!sums_out || !lineages_out) return fail(EPIPF_EINVAL, "NULL argument");
     if (lineage != EPIPF_LINEAGE_REFERENCE && lineage != EPIPF_LINEAGE_GENEALOGY)
         return fail(EPIPF_EINVAL, "unknown lineage %d", lineage);
@@ -1274,7 +1280,7 @@ static int smooth_run(epipf_ctx* c, int n, int T, int N, int C, const int32_t* u
     const size_t ob_q = n_q > 0 ? align256((size_t)n * n_q * TC * sizeof(int32_t)) : 0;
     const size_t ob_r = n_q > 0 ? align256((size_t)n_q * sizeof(uint32_t)) : 0;
     const size_t sb_h = align256((size_t)slice * hb1), sb_m = align256((size_t)slice * mb1);
-    const size_t ub_h = up_hidden ? align256((size_t)n * T * N * C * sizeof(int32_t)) : 0;
+    const size_t ub_h = (up_hidden || flows) ? align256((size_t)n * T * N * C * sizeof(int32_t)) : 0;
     const size_t ub_a = up_hidden ? align256((size_t)n * T * N * sizeof(int32_t)) : 0;
     if (ensure_scratch(c, ob_s + ob_l + ob_q + ob_r + sb_h + sb_m + ub_h + ub_a)) return EPIPF_ENOMEM;
     char* p = (char*)c->scratch;
@@ -1302,6 +1308,14 @@ static int smooth_run(epipf_ctx* c, int n, int T, int N, int C, const int32_t* u
         HIP_TRY(hipMemcpyAsync(danc, up_ancestry, sizeof(int32_t) * (size_t)n * T * N, hipMemcpyHostToDevice, c->stream));
         a.hidden = dhid; a.ancestry = danc; a.status = nullptr;
         a.hist_stride = (size_t)T * N * C; a.anc_stride = (size_t)T * N;
+    } else if (flows) {
+        IncidenceFlowArgs fa{};
+        fa.n = n; fa.T = T; fa.N = N; fa.hist_stride = c->hist_stride; fa.anc_stride = c->anc_stride;
+        fa.hidden = c->hidden; fa.ancestry = c->ancestry; fa.flow = dhid;
+        const hipError_t fe = launch_incidence_flows(fa, c->model, c->stream);
+        if (fe != hipSuccess) return fail(EPIPF_EHIP, "flow launch failed: %s", hipGetErrorString(fe));
+        a.hidden = dhid; a.ancestry = c->ancestry; a.status = c->status;
+        a.hist_stride = (size_t)T * N * C; a.anc_stride = c->anc_stride;
     } else {
         a.hidden = c->hidden; a.ancestry = c->ancestry; a.status = c->status;
         a.hist_stride = c->hist_stride; a.anc_stride = c->anc_stride;
@@ -1419,6 +1433,7 @@ static int if2_impl(epipf_ctx* c, bool subgroups, int n_searches, int iterations
     }
     HIP_TRY(hipSetDevice(c->device));
     c->walk_valid = false;                               // the history is this call's from here on
+    c->inc_valid = false;
     // scratch: swarm [2][max_chains][d][N] | start [max_chains][d][N] | log_zeta [M][max_chains][T] | mean [S][M][d] | done [S]
     const size_t comp = (size_t)d * N, mc = (size_t)c->max_chains;
     const size_t b_swarm = align256(sizeof(double) * 2 * mc * comp), b_start = align256(sizeof(double) * mc * comp);
@@ -1522,6 +1537,24 @@ int epipf_iterated_filtering_subgroups(epipf_ctx* c, int n_searches, int iterati
                     log_zetas_out, mean_out, iterations_done_out, status_out);
 }
 
+// theta_hist [S][T][d][N] of the random-walk filters (epipf_walk_filter, epipf_incidence_walk): grown when a call needs more.
+static int ensure_walk_theta(epipf_ctx* c, int S, int T, int d, int N) {
+    const size_t need = sizeof(double) * (size_t)S * T * d * N;
+    if (need > c->walk_bytes) {
+        if (c->walk_theta) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->walk_theta); }
+        c->walk_theta = nullptr;
+        c->walk_bytes = 0;
+        if (hipMalloc((void**)&c->walk_theta, need) != hipSuccess) {
+            c->walk_theta = nullptr;
+            (void)hipGetLastError();
+            return fail(EPIPF_ENOMEM, "the parameter history needs %zu bytes (%d chains x %d days x %d x %d doubles): hipMalloc failed",
+                        need, S, T, d, N);
+        }
+        c->walk_bytes = need;
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------------ time-varying rates
 // The random-walk filter: epipf_if2's pass at one iteration with a half-width vector per chain, every day's swarm kept
 // in theta_hist.  hidden, ancestry, status and log_zeta are the context's own, so epipf_copy_history, epipf_path_sample
@@ -1548,20 +1581,9 @@ int epipf_walk_filter(epipf_ctx* c, int n_chains, const double* swarm_in, int d,
     }
     HIP_TRY(hipSetDevice(c->device));
     c->walk_valid = false;
+    c->inc_valid = false;
     const size_t comp = (size_t)d * N, stride = (size_t)T * comp;
-    const size_t need = sizeof(double) * (size_t)S * stride;
-    if (need > c->walk_bytes) {
-        if (c->walk_theta) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->walk_theta); }
-        c->walk_theta = nullptr;
-        c->walk_bytes = 0;
-        if (hipMalloc((void**)&c->walk_theta, need) != hipSuccess) {
-            c->walk_theta = nullptr;
-            (void)hipGetLastError();
-            return fail(EPIPF_ENOMEM, "the parameter history needs %zu bytes (%d chains x %d days x %d x %d doubles): hipMalloc failed",
-                        need, S, T, d, N);
-        }
-        c->walk_bytes = need;
-    }
+    if (const int e = ensure_walk_theta(c, S, T, d, N)) return e;
     // scratch: start [S][d][N] | hw [S][d]
     const size_t b_start = align256(sizeof(double) * (size_t)S * comp), b_hw = align256(sizeof(double) * (size_t)S * d);
     if (ensure_scratch(c, b_start + b_hw)) return EPIPF_ENOMEM;
@@ -1612,6 +1634,67 @@ int epipf_walk_filter(epipf_ctx* c, int n_chains, const double* swarm_in, int d,
 }
 
 // ------------------------------------------------------------------------ incidence observations
+// What epipf_run_incidence and epipf_incidence_walk share.  incidence_rows: the reports checked and padded to rows
+// [D + 2][F] (rows 0 and D + 1 all NaN) with the reported-column masks rep [D + 2].  incidence_probs: a chain's probs.
+// ensure_incidence_counts / ensure_incidence_acc: the device buffers of the reports and of the accumulator
+// int32 [2][S][F][N], grown when a call needs more, the latter within its budget.
+static int incidence_rows(const double* counts, int D, int F, int obs_model, std::vector<double>& rows,
+                          std::vector<uint8_t>& rep) {
+    const int T = D + 2;
+    rows.assign((size_t)T * F, NAN);
+    rep.assign((size_t)T, 0);
+    for (size_t i = 0; i < (size_t)D * F; ++i) {
+        const double y = counts[i];
+        if (std::isnan(y)) continue;                                     // not reported
+        if (std::isinf(y) || y < 0.0)
+            return fail(EPIPF_EINVAL, "counts[%zu][%zu]=%g: a report must be finite and >= 0 (NaN: not reported)", i / F, i % F, y);
+        if (obs_model == EPIPF_OBS_BINOMIAL && y != std::floor(y))
+            return fail(EPIPF_EINVAL, "counts[%zu][%zu]=%g: the binomial model needs integer reports", i / F, i % F, y);
+        rows[(size_t)F + i] = y;
+        rep[1 + i / F] |= (uint8_t)(1u << (i % F));
+    }
+    return 0;
+}
+
+static int incidence_probs(int ch, double pr, int obs_model) {
+    if (!(pr >= 0.0 && pr < INFINITY && (obs_model == EPIPF_OBS_NORMAL || pr <= 1.0)))
+        return fail(EPIPF_EINVAL, "probs[%d]=%g: %s", ch, pr,
+                    obs_model == EPIPF_OBS_NORMAL ? "the noise ratio must be finite and >= 0"
+                                                  : "the reporting probability must lie in [0, 1]");
+    return 0;
+}
+
+static int ensure_incidence_counts(epipf_ctx* c, size_t n) {
+    if (n > c->inc_counts_n) {
+        if (c->inc_counts) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->inc_counts); }
+        c->inc_counts = nullptr;
+        c->inc_counts_n = 0;
+        if (dalloc(&c->inc_counts, n)) return EPIPF_ENOMEM;
+        c->inc_counts_n = n;
+    }
+    return 0;
+}
+
+static int ensure_incidence_acc(epipf_ctx* c, int S, int F, int N) {
+    const size_t need = 2 * sizeof(int32_t) * (size_t)S * F * N;
+    if (need > c->inc_acc_bytes) {
+        if (c->inc_acc_limit && need > c->inc_acc_limit)
+            return fail(EPIPF_ENOMEM, "the accumulator needs %zu bytes (2 x %d chains x %d columns x %d int32): over the budget of %zu bytes",
+                        need, S, F, N, c->inc_acc_limit);
+        if (c->inc_acc) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->inc_acc); }
+        c->inc_acc = nullptr;
+        c->inc_acc_bytes = 0;
+        if (hipMalloc((void**)&c->inc_acc, need) != hipSuccess) {
+            c->inc_acc = nullptr;
+            (void)hipGetLastError();
+            return fail(EPIPF_ENOMEM, "the accumulator needs %zu bytes (2 x %d chains x %d columns x %d int32): hipMalloc failed",
+                        need, S, F, N);
+        }
+        c->inc_acc_bytes = need;
+    }
+    return 0;
+}
+
 // The filter on reported transition counts: T = D + 2 rows (row 0 the initial draw, rows 1..D the days, row D + 1 one more
 // resampling on day D's weights), weights from the particles' flows (epipf_incidence.hpp).  hidden, ancestry, status and
 // log_zeta are the context's own and the run length becomes D + 2, so epipf_copy_history, epipf_path_sample, epipf_smooth
@@ -1630,18 +1713,9 @@ int epipf_run_incidence(epipf_ctx* c, int n_chains, const double* theta, int d, 
     if (obs_model != EPIPF_OBS_BINOMIAL && obs_model != EPIPF_OBS_NORMAL) return fail(EPIPF_EINVAL, "bad obs_model %d", obs_model);
     if (D < 1 || (long long)D + 2 > c->Tmax) return fail(EPIPF_EINVAL, "D=%d: D + 2 rows outside [3, t_max=%d]", D, c->Tmax);
     const int T = D + 2;
-    std::vector<double> rows((size_t)T * F, NAN);
-    std::vector<uint8_t> rep((size_t)T, 0);
-    for (size_t i = 0; i < (size_t)D * F; ++i) {
-        const double y = counts[i];
-        if (std::isnan(y)) continue;                                     // not reported
-        if (std::isinf(y) || y < 0.0)
-            return fail(EPIPF_EINVAL, "counts[%zu][%zu]=%g: a report must be finite and >= 0 (NaN: not reported)", i / F, i % F, y);
-        if (obs_model == EPIPF_OBS_BINOMIAL && y != std::floor(y))
-            return fail(EPIPF_EINVAL, "counts[%zu][%zu]=%g: the binomial model needs integer reports", i / F, i % F, y);
-        rows[(size_t)F + i] = y;
-        rep[1 + i / F] |= (uint8_t)(1u << (i % F));
-    }
+    std::vector<double> rows;
+    std::vector<uint8_t> rep;
+    if (const int e = incidence_rows(counts, D, F, obs_model, rows, rep)) return e;
     for (int ch = 0; ch < S; ++ch) {
         const bool on = !active || active[ch];
         ChainParam& q = c->h_cp[ch];
@@ -1653,42 +1727,19 @@ int epipf_run_incidence(epipf_ctx* c, int n_chains, const double* theta, int d, 
             set_theta(q, nullptr, i, v);
         }
         const double pr = probs[ch];
-        if (on && !(pr >= 0.0 && pr < INFINITY && (obs_model == EPIPF_OBS_NORMAL || pr <= 1.0)))
-            return fail(EPIPF_EINVAL, "probs[%d]=%g: %s", ch, pr,
-                        obs_model == EPIPF_OBS_NORMAL ? "the noise ratio must be finite and >= 0"
-                                                      : "the reporting probability must lie in [0, 1]");
+        if (on)
+            if (const int e = incidence_probs(ch, pr, obs_model)) return e;
         set_chain_stream(c, q, pr, keys[ch], filter_index[ch]);
         q.skip = on ? 0 : 1;
         q.chosen = -1;
     }
     HIP_TRY(hipSetDevice(c->device));
     c->walk_valid = false;                               // the history is this run's from here on
-    if (rows.size() > c->inc_counts_n) {
-        if (c->inc_counts) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->inc_counts); }
-        c->inc_counts = nullptr;
-        c->inc_counts_n = 0;
-        if (dalloc(&c->inc_counts, rows.size())) return EPIPF_ENOMEM;
-        c->inc_counts_n = rows.size();
-    }
+    c->inc_valid = false;
+    if (const int e = ensure_incidence_counts(c, rows.size())) return e;
     const size_t acc_half = (size_t)S * F * N;
-    if (cumulate) {
-        const size_t need = 2 * sizeof(int32_t) * acc_half;
-        if (need > c->inc_acc_bytes) {
-            if (c->inc_acc_limit && need > c->inc_acc_limit)
-                return fail(EPIPF_ENOMEM, "the accumulator needs %zu bytes (2 x %d chains x %d columns x %d int32): over the budget of %zu bytes",
-                            need, S, F, N, c->inc_acc_limit);
-            if (c->inc_acc) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->inc_acc); }
-            c->inc_acc = nullptr;
-            c->inc_acc_bytes = 0;
-            if (hipMalloc((void**)&c->inc_acc, need) != hipSuccess) {
-                c->inc_acc = nullptr;
-                (void)hipGetLastError();
-                return fail(EPIPF_ENOMEM, "the accumulator needs %zu bytes (2 x %d chains x %d columns x %d int32): hipMalloc failed",
-                            need, S, F, N);
-            }
-            c->inc_acc_bytes = need;
-        }
-    }
+    if (cumulate)
+        if (const int e = ensure_incidence_acc(c, S, F, N)) return e;
     // rows and rep stay alive past the stream synchronisation below
     HIP_TRY(hipMemcpyAsync(c->cp, c->h_cp, sizeof(ChainParam) * S, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->inc_counts, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice, c->stream));
@@ -1731,7 +1782,115 @@ int epipf_run_incidence(epipf_ctx* c, int n_chains, const double* theta, int d, 
     c->last_chains = S;
     c->last_T = T;
     c->have_run = true;
+    c->inc_valid = true;
     return EPIPF_OK;
+}
+
+// ------------------------------------------------------------------------ R_t from case counts
+// The random-walk filter on reported transition counts: epipf_walk_filter's swarm, half-widths and theta_hist under
+// epipf_run_incidence's rows, reports and accumulator (epipf_walk_incidence.hpp).  The run length becomes D + 2 and the
+// parameter history is the context's, so the history calls of both parents see the pass afterwards.
+int epipf_incidence_walk(epipf_ctx* c, int n_chains, const double* swarm_in, int d, const double* half_widths, int obs_model,
+                         const double* probs, const uint64_t* keys, const uint32_t* filter_index, const double* counts,
+                         int D, int cumulate, double* log_zetas_out, int32_t* status_out) {
+    if (!c || !swarm_in || !half_widths || !probs || !keys || !filter_index || !counts || !log_zetas_out || !status_out)
+        return fail(EPIPF_EINVAL, "NULL argument");
+    if (c->model != EPIPF_SIR && c->model != EPIPF_SEIR)
+        return fail(EPIPF_EINVAL, "the random-walk filter on incidence covers the SIR and SEIR models; the subgroup models are out of its scope");
+    if (!c->have_pop) return fail(EPIPF_ESTATE, "epipf_set_population was not called");
+    const int S = n_chains, N = c->N, F = incidence_flows(c->model);
+    if (d != theta_dim(c->model, c->G)) return fail(EPIPF_EINVAL, "theta has %d entries per particle, model needs %d", d, theta_dim(c->model, c->G));
+    if (S < 1 || S > c->max_chains) return fail(EPIPF_EINVAL, "n_chains=%d outside [1, max_chains=%d]", S, c->max_chains);
+    if (obs_model != EPIPF_OBS_BINOMIAL && obs_model != EPIPF_OBS_NORMAL) return fail(EPIPF_EINVAL, "bad obs_model %d", obs_model);
+    if (D < 1 || (long long)D + 2 > c->Tmax) return fail(EPIPF_EINVAL, "D=%d: D + 2 rows outside [3, t_max=%d]", D, c->Tmax);
+    const int T = D + 2;
+    if (const int e = check_swarm(half_widths, (size_t)S, swarm_in, (size_t)S, N, d)) return e;
+    std::vector<double> rows;
+    std::vector<uint8_t> rep;
+    if (const int e = incidence_rows(counts, D, F, obs_model, rows, rep)) return e;
+    for (int s = 0; s < S; ++s) {
+        if (const int e = incidence_probs(s, probs[s], obs_model)) return e;
+        ChainParam& q = c->h_cp[s];
+        memset(&q, 0, sizeof q);                         // theta is the particles' own
+        set_chain_stream(c, q, probs[s], keys[s], filter_index[s]);
+        q.chosen = -1;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    c->walk_valid = false;                               // the history is this call's from here on
+    c->inc_valid = false;
+    const size_t comp = (size_t)d * N, stride = (size_t)T * comp;
+    if (const int e = ensure_walk_theta(c, S, T, d, N)) return e;
+    if (const int e = ensure_incidence_counts(c, rows.size())) return e;
+    const size_t acc_half = (size_t)S * F * N;
+    if (cumulate)
+        if (const int e = ensure_incidence_acc(c, S, F, N)) return e;
+    // scratch: start [S][d][N] | hw [S][d]
+    const size_t b_start = align256(sizeof(double) * (size_t)S * comp), b_hw = align256(sizeof(double) * (size_t)S * d);
+    if (ensure_scratch(c, b_start + b_hw)) return EPIPF_ENOMEM;
+    double* d_start = (double*)c->scratch;
+    double* d_hw = (double*)((char*)c->scratch + b_start);
+    std::vector<double> soa((size_t)S * comp);            // [S][N][d] -> [S][d][N]
+    for (int s = 0; s < S; ++s)
+        for (int j = 0; j < N; ++j)
+            for (int k = 0; k < d; ++k) soa[((size_t)s * d + k) * N + j] = swarm_in[((size_t)s * N + j) * d + k];
+    // rows, rep and soa stay alive past the stream synchronisation below
+    HIP_TRY(hipMemcpyAsync(c->cp, c->h_cp, sizeof(ChainParam) * S, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_start, soa.data(), sizeof(double) * soa.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_hw, half_widths, sizeof(double) * (size_t)S * d, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->inc_counts, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->log_zeta, 0xFF, sizeof(double) * (size_t)S * T, c->stream));   // rows never written read as NaN
+    const size_t b_counters = sizeof(unsigned long long) * (size_t)kCounterSlots * kCounterStride;
+    HIP_TRY(hipMemsetAsync(c->counters, 0, b_counters, c->stream));
+
+    WalkIncidenceArgs a{};
+    StepArgs& s = a.s;
+    one_lane_step_args(c, T, s);
+    s.Y = nullptr;                                       // the reports are a.counts
+    a.d = d; a.hw = d_hw; a.start = d_start; a.hist = c->walk_theta; a.chain_stride = stride;
+    a.counts = c->inc_counts; a.acc = cumulate ? c->inc_acc : nullptr; a.acc_half = acc_half;
+
+    FilterStreams fs{};
+    if (const int e = fork_streams(c, std::min(c->n_streams, S), fs)) return e;
+    const hipError_t le = launch_walk_incidence(a, c->model, obs_model, cumulate != 0, rep.data(), S, fs);
+    if (le != hipSuccess) return fail(EPIPF_EHIP, "kernel launch failed: %s", hipGetErrorString(le));
+    HIP_TRY(hipMemcpyAsync(log_zetas_out, c->log_zeta, sizeof(double) * (size_t)S * T, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(status_out, c->status, sizeof(int32_t) * S, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_counters, c->counters, b_counters, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemsetAsync(c->counters, 0, b_counters, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    harvest_counters(c, s.count_events != 0, false);
+    // a chain that died at step p wrote -inf there and nothing after: its later rows are -inf as well
+    for (int q = 0; q < S; ++q)
+        if (status_out[q] == EPIPF_STATUS_DEGENERATE)
+            for (int p = 0; p < T; ++p)
+                if (std::isnan(log_zetas_out[(size_t)q * T + p])) log_zetas_out[(size_t)q * T + p] = -INFINITY;
+    c->stats.particle_steps += (int64_t)S * N * T;
+    c->stats.filters += S;
+    c->stats.last_lanes = 1;
+    c->stats.last_lane_events = 1;
+    c->stats.last_fused = 0;
+    c->last_chains = S;
+    c->last_T = T;
+    c->have_run = true;
+    c->walk_valid = true;
+    c->inc_valid = true;
+    trim_scratch(c);
+    return EPIPF_OK;
+}
+
+// The smoothed true flows of the last incidence pass: the flows of every particle formed on the device from the
+// resident history (launch_incidence_flows, into smooth_run's scratch) and reduced by the smoother's kernels as a
+// history of F compartments under the genealogy's multiplicities.
+int epipf_incidence_smooth(epipf_ctx* c, int n_chains, int lag, const double* q, int n_q, int bins, int64_t* sums_out,
+                           int32_t* quant_out, int32_t* lineages_out) {
+    if (!c) return fail(EPIPF_EINVAL, "NULL context");
+    if (!c->inc_valid)
+        return fail(EPIPF_ESTATE, c->have_run ? "the context's history is no longer an incidence pass's: another run overwrote it"
+                                              : "no incidence pass has run on this context");
+    if (n_chains < 1 || n_chains > c->last_chains) return fail(EPIPF_EINVAL, "n_chains=%d outside [1, %d]", n_chains, c->last_chains);
+    return smooth_run(c, n_chains, c->last_T, c->N, incidence_flows(c->model), nullptr, nullptr, EPIPF_LINEAGE_GENEALOGY,
+                      EPIPF_SMOOTH_SMOOTHING, lag < 0 ? kSmoothNoLag : lag, q, n_q, bins, sums_out, quant_out, lineages_out,
+                      true);
 }
 
 static int walk_state(const epipf_ctx* c, int n_chains) {

@@ -44,21 +44,6 @@ __global__ __launch_bounds__(64) void incidence_init_kernel(IncidenceArgs a) {
     init_weights<WG>(s, smem, bp, j, j < s.N, true, WG - 1, [] { return 1.0; });
 }
 
-// One column's factor: oracle.binom_pmf(y, n, p) = exp(hi) (1 + lo) of the compensated log pmf with its special cases
-// (NaN for a bad p, 0 outside the support), or oracle.norm_pdf(y, n, probs).
-template <int OBS>
-__device__ __forceinline__ double incidence_factor(double y, double n, const ChainParam& cp, const double* lf,
-                                                   int lf_max) {
-    if constexpr (OBS == kNormal) {
-        return normal_pdf(y, n, cp.probs);
-    } else {
-        const LogW L = binom_logpmf(y, n, cp, lf, lf_max);
-        if (isnan(L.hi)) return L.hi;
-        const double e = exp(L.hi);
-        return fma(e, L.lo, e);
-    }
-}
-
 // rep_prev / rep_cur: bit k set where column k of day p - 1 / day p is reported
 template <int MODEL, int OBS, bool CUM>
 __global__ __launch_bounds__(64) void incidence_step_kernel(IncidenceArgs a, int p, int rep_prev, int rep_cur) {

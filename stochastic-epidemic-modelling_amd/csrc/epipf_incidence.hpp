@@ -30,4 +30,20 @@ struct IncidenceArgs {
 hipError_t launch_incidence(const IncidenceArgs& a, int model, int obs, bool cumulate, const uint8_t* rep, int n_chains,
                             const FilterStreams& fs);
 
+// One column's factor: oracle.binom_pmf(y, n, p) = exp(hi) (1 + lo) of the compensated log pmf with its special cases
+// (NaN for a bad p, 0 outside the support), or oracle.norm_pdf(y, n, probs).  Shared by the step kernels of
+// epipf_incidence.hip and epipf_walk_incidence.hip.
+template <int OBS>
+__device__ __forceinline__ double incidence_factor(double y, double n, const ChainParam& cp, const double* lf,
+                                                   int lf_max) {
+    if constexpr (OBS == kNormal) {
+        return normal_pdf(y, n, cp.probs);
+    } else {
+        const LogW L = binom_logpmf(y, n, cp, lf, lf_max);
+        if (isnan(L.hi)) return L.hi;
+        const double e = exp(L.hi);
+        return fma(e, L.lo, e);
+    }
+}
+
 }  // namespace epipf

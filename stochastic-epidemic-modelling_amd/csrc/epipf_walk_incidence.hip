@@ -1,0 +1,251 @@
+// epipf_walk_incidence.hip -- time-varying rates from reported case counts on MI355X (gfx950), DESIGN.md §20
+// (epipf_walk_incidence.hpp).
+//
+// walk_incidence_init_kernel / walk_incidence_step_kernel: one lane per particle, one wave per block, on the shared
+// phases of epipf_step.hpp (step_total, step_degenerate, step_log_zeta, step_ancestor, step_count, step_store_weights,
+// init_state, init_weights).  The middle of the step is the union of its two parents':
+//   from walk_step_kernel (epipf_walk.hip)
+//   - every chain starts (status OK); the half-widths read per chain from a device array;
+//   - step p gathers the ancestor's theta from row p - 1 of theta_hist, jitters it (if2_perturb_hw at step p, domain 7)
+//     and stores it as row p: this particle's rates for the per-lane SSA (the certified f32 loop, then the exact loop
+//     for the lanes it hands back);
+//   from incidence_step_kernel (epipf_incidence.hip)
+//   - T = D + 2 rows, row 0 weighs 1; the parent state stays in registers across the propagate (int32 [C]);
+//   - the day's flows are differences of the parent and the new state; with CUM, a column that was not reported on day
+//     p - 1 adds the ancestor's accumulator of that day;
+//   - the weight is the product over the reported columns, in column order from 1.0, of incidence_factor; the
+//     reported-column masks of days p - 1 and p are kernel arguments, hence wave-uniform.
+// No Philox domain, counter layout or stream of its own: the draws are the resampling uniforms, the jitter's and the
+// SSA's.  incidence_flows_kernel forms the true flows of a resident history for the smoother.
+#include "epipf_walk_incidence.hpp"
+
+#include <algorithm>
+
+#include "epipf_if2_perturb.hpp"
+#include "epipf_step.hpp"
+
+namespace epipf {
+
+template <int MODEL>
+__global__ __launch_bounds__(64) void walk_incidence_init_kernel(WalkIncidenceArgs a) {
+    constexpr int C = Shape<MODEL, 1>::C;
+    constexpr int D = (MODEL == kSIR) ? 2 : 3;
+    constexpr int F = incidence_flows(MODEL);
+    constexpr int WG = 64;
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const StepArgs& s = a.s;
+    const BlockPos bp = step_block(s);
+    const int chain = bp.chain;
+    const int j = bp.b * WG + (int)threadIdx.x;
+    const ChainParam cp = s.cp[chain];
+    if (bp.b == 0 && threadIdx.x == 0) s.status[chain] = kStatusOk;
+    if (j < s.N) {
+        double x[C];
+        init_particle<MODEL, 1>(s, cp, j, x);
+        init_state<C>(s, chain, j, x);
+        if (a.acc) {                                                     // acc_0 = 0, buffer 0
+#pragma unroll
+            for (int k = 0; k < F; ++k) a.acc[((size_t)chain * F + k) * s.N + j] = 0;
+        }
+        double th[D], hw[D];
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+            th[c] = a.start[((size_t)chain * D + c) * s.N + j];
+            hw[c] = a.hw[(size_t)chain * D + c];
+        }
+        if2_perturb_hw<D>(th, hw, (uint32_t)j, kDomainIf2, cp);          // step 0
+        double* row = a.hist + (size_t)chain * a.chain_stride;           // row 0
+#pragma unroll
+        for (int c = 0; c < D; ++c) row[(size_t)c * s.N + j] = th[c];
+    }
+    // row 0 is never reported: every particle weighs 1 (lanes past N: 0)
+    init_weights<WG>(s, smem, bp, j, j < s.N, true, WG - 1, [] { return 1.0; });
+}
+
+// rep_prev / rep_cur: bit k set where column k of day p - 1 / day p is reported
+template <int MODEL, int OBS, bool CUM>
+__global__ __launch_bounds__(64) void walk_incidence_step_kernel(WalkIncidenceArgs a, int p, int rep_prev, int rep_cur) {
+    constexpr int C = Shape<MODEL, 1>::C;
+    constexpr int D = (MODEL == kSIR) ? 2 : 3;
+    constexpr int F = incidence_flows(MODEL);
+    constexpr int WG = 64;
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const StepArgs& s = a.s;
+    LogTab* tab = step_logtab(smem);
+    const BlockPos bp = step_block(s);
+    const int chain = bp.chain;
+    const int tid = threadIdx.x;
+    const int j = bp.b * WG + tid;
+    if (s.status[chain] != 0) return;
+    const ChainParam cp = s.cp[chain];
+    const int prev = (p - 1) & 1, cur = p & 1;            // the accumulator's halves, as the weights' (step_half)
+    const size_t wprev = step_half(s, chain, p - 1, s.wstride), wcur = step_half(s, chain, p, s.wstride);
+    const size_t bprev = step_half(s, chain, p - 1, s.bstride), bcur = step_half(s, chain, p, s.bstride);
+    const double total = step_total(s, smem, bprev);
+    if (!(total > 0.0)) {
+        step_degenerate(s, bp, p);
+        return;
+    }
+    step_log_zeta(s, bp, p, total);
+    int anc = step_ancestor<false>(s, smem, cp, p, j, total, wprev, bprev);
+    // the parent state: propagated in x, kept in xp for the flows; the ancestor's theta of row p - 1, jittered and kept
+    // as row p's: this particle's rates
+    double x[C];
+    int32_t xp[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) { x[c] = 0.0; xp[c] = 0; }
+    const uint32_t ptag = ((uint32_t)p & 0xFFFFFFu) | kDomainSSA;
+    ChainParam lcp = cp;
+    bool fast_ok = true, eligible = false;
+    int nev = 0, iters = 0;
+    if (j < s.N) {
+        anc = checked_index(anc, s.N);
+        s.ancestry[(size_t)chain * s.anc_stride + (size_t)p * s.N + j] = anc;
+        const double* from = a.hist + (size_t)chain * a.chain_stride + (size_t)(p - 1) * D * s.N;
+        double* to = a.hist + (size_t)chain * a.chain_stride + (size_t)p * D * s.N;
+        double th[D], hw[D];
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+            th[c] = from[(size_t)c * s.N + anc];
+            hw[c] = a.hw[(size_t)chain * D + c];
+        }
+        if2_perturb_hw<D>(th, hw, (uint32_t)j, ((uint32_t)p & 0xFFFFFFu) | kDomainIf2, cp);
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+            to[(size_t)c * s.N + j] = th[c];
+            lcp.theta[c] = th[c];
+            lcp.thetaf[c] = (float)th[c];
+        }
+        const int32_t* hp = s.hidden + (size_t)chain * s.hist_stride + ((size_t)(p - 1) * s.N + anc) * C;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            xp[c] = hp[c];
+            x[c] = (double)xp[c];
+        }
+        fast_ok = fast_propagate<MODEL, 1>(x, lcp, (uint32_t)j, ptag, 1.0, nev, iters, eligible);
+    }
+    // lanes the f32 loop could not run or could not certify: the exact loop from the untouched parent state, per lane
+    // (one wave per block, so the test is block-uniform and the barrier legal)
+    if (__any(!fast_ok)) {
+        for (int i = tid; i < kLogTabEntries; i += WG) tab[i] = s.logtab[i];
+        __syncthreads();
+        if (!fast_ok) nev = exact_propagate<MODEL, 1>(x, lcp, (uint32_t)j, ptag, 1.0, tab, iters);
+    }
+    step_count(s, nev, iters, !fast_ok);                 // lanes past N hold fast_ok = true
+    double w = 0.0;
+    if (j < s.N) {
+        int32_t xn[C];
+        int32_t* hc = s.hidden + (size_t)chain * s.hist_stride + ((size_t)p * s.N + j) * C;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            xn[c] = (int32_t)x[c];
+            hc[c] = xn[c];
+        }
+        if (p + 1 < s.T) {                               // the last row is weighted by nothing and followed by no step
+            int32_t acc[F];
+            acc[0] = xp[0] - xn[0];                                              // S' - S
+            if constexpr (MODEL == kSIR) {
+                acc[1] = xn[2] - xp[2];                                          // R - R'
+            } else {
+                acc[1] = (xn[2] + xn[3]) - (xp[2] + xp[3]);                      // (I + R) - (I' + R')
+                acc[2] = xn[3] - xp[3];                                          // R - R'
+            }
+            if constexpr (CUM) {
+                const int32_t* from = a.acc + (size_t)prev * a.acc_half + (size_t)chain * F * s.N;
+                int32_t* to = a.acc + (size_t)cur * a.acc_half + (size_t)chain * F * s.N;
+#pragma unroll
+                for (int k = 0; k < F; ++k) {
+                    if (!((rep_prev >> k) & 1)) acc[k] += from[(size_t)k * s.N + anc];   // uniform branch
+                    to[(size_t)k * s.N + j] = acc[k];
+                }
+            }
+            w = 1.0;
+            const double* yrow = a.counts + (size_t)p * F;
+#pragma unroll
+            for (int k = 0; k < F; ++k)
+                if ((rep_cur >> k) & 1)                                                  // uniform branch
+                    w = w * incidence_factor<OBS>(yrow[k], (double)acc[k], cp, s.lf, s.lf_max);
+        }
+    }
+    step_store_weights(s, smem, bp.b, j, p, w, wcur, bcur);
+}
+
+template <int MODEL, int OBS, bool CUM>
+static hipError_t launch_walk_incidence_t(const WalkIncidenceArgs& a, const uint8_t* rep, int n_chains,
+                                          const FilterStreams& fs) {
+    const StepArgs& s0 = a.s;
+    const size_t lds = step_lds_bytes(s0.B, 64);
+    launch_chain_groups(s0, n_chains, fs, 64, [&](int, const StepArgs& sg, int, dim3 grid, hipStream_t st) {
+        WalkIncidenceArgs ag = a;
+        ag.s = sg;
+        hipLaunchKernelGGL((walk_incidence_init_kernel<MODEL>), grid, dim3(64), lds, st, ag);
+        for (int p = 1; p < s0.T; ++p)
+            hipLaunchKernelGGL((walk_incidence_step_kernel<MODEL, OBS, CUM>), grid, dim3(64), lds, st, ag, p,
+                               (int)rep[p - 1], (int)rep[p]);
+    });
+    return hipGetLastError();
+}
+
+template <int MODEL>
+static hipError_t launch_walk_incidence_m(const WalkIncidenceArgs& a, int obs, bool cumulate, const uint8_t* rep,
+                                          int n_chains, const FilterStreams& fs) {
+    if (obs == kBinomial)
+        return cumulate ? launch_walk_incidence_t<MODEL, kBinomial, true>(a, rep, n_chains, fs)
+                        : launch_walk_incidence_t<MODEL, kBinomial, false>(a, rep, n_chains, fs);
+    return cumulate ? launch_walk_incidence_t<MODEL, kNormal, true>(a, rep, n_chains, fs)
+                    : launch_walk_incidence_t<MODEL, kNormal, false>(a, rep, n_chains, fs);
+}
+
+hipError_t launch_walk_incidence(const WalkIncidenceArgs& a, int model, int obs, bool cumulate, const uint8_t* rep,
+                                 int n_chains, const FilterStreams& fs) {
+    if (a.s.wg != 64 || a.s.lanes != 1 || a.s.T < 3 || !a.counts || !rep || (cumulate && !a.acc) || !a.hw || !a.start ||
+        !a.hist)
+        return hipErrorInvalidValue;
+    if (obs != kBinomial && obs != kNormal) return hipErrorInvalidValue;
+    if (model == kSIR && a.d == 2) return launch_walk_incidence_m<kSIR>(a, obs, cumulate, rep, n_chains, fs);
+    if (model == kSEIR && a.d == 3) return launch_walk_incidence_m<kSEIR>(a, obs, cumulate, rep, n_chains, fs);
+    return hipErrorInvalidValue;
+}
+
+// ------------------------------------------------------------------------------------------------ the true flows
+// One thread per (chain, row, particle), blockIdx.y the chain; every thread writes its F entries (row 0: zeros).
+template <int MODEL>
+__global__ __launch_bounds__(256) void incidence_flows_kernel(IncidenceFlowArgs a) {
+    constexpr int C = Shape<MODEL, 1>::C;
+    constexpr int F = incidence_flows(MODEL);
+    const size_t rows = (size_t)a.T * a.N;
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;      // p N + i
+    if (t >= rows) return;
+    const int chain = (int)blockIdx.y;
+    const int p = (int)(t / (size_t)a.N);
+    int32_t f[F];
+#pragma unroll
+    for (int k = 0; k < F; ++k) f[k] = 0;
+    if (p >= 1) {
+        const int anc = checked_index(a.ancestry[(size_t)chain * a.anc_stride + t], a.N);
+        const int32_t* xn = a.hidden + (size_t)chain * a.hist_stride + t * C;
+        const int32_t* xp = a.hidden + (size_t)chain * a.hist_stride + ((size_t)(p - 1) * a.N + anc) * C;
+        f[0] = xp[0] - xn[0];                                                    // S' - S
+        if constexpr (MODEL == kSIR) {
+            f[1] = xn[2] - xp[2];                                                // R - R'
+        } else {
+            f[1] = (xn[2] + xn[3]) - (xp[2] + xp[3]);                            // (I + R) - (I' + R')
+            f[2] = xn[3] - xp[3];                                                // R - R'
+        }
+    }
+    int32_t* out = a.flow + ((size_t)chain * rows + t) * F;
+#pragma unroll
+    for (int k = 0; k < F; ++k) out[k] = f[k];
+}
+
+hipError_t launch_incidence_flows(const IncidenceFlowArgs& a, int model, hipStream_t s) {
+    if (a.n < 1 || a.n > 65535 || a.T < 1 || a.N < 1 || !a.hidden || !a.ancestry || !a.flow) return hipErrorInvalidValue;
+    const size_t rows = (size_t)a.T * a.N;
+    const dim3 grid((unsigned)((rows + 255) / 256), (unsigned)a.n), block(256);
+    if (model == kSIR) hipLaunchKernelGGL(incidence_flows_kernel<kSIR>, grid, block, 0, s, a);
+    else if (model == kSEIR) hipLaunchKernelGGL(incidence_flows_kernel<kSEIR>, grid, block, 0, s, a);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+}  // namespace epipf

@@ -30,7 +30,7 @@ EXPORTS = (
     "epipf_forecast", "epipf_abc_smc_generation", "epipf_abc_smc_weights", "epipf_smooth", "epipf_smooth_history",
     "epipf_iterated_filtering_subgroups", "epipf_smooth_lag", "epipf_smooth_lag_history", "epipf_forecast_summary",
     "epipf_walk_filter", "epipf_walk_history", "epipf_walk_smooth", "epipf_walk_smooth_history",
-    "epipf_run_incidence",
+    "epipf_run_incidence", "epipf_incidence_walk", "epipf_incidence_smooth",
 )
 # Entry points whose names carry a digit, listed apart: EXPORTS is compared with the header's names as a letters-only
 # pattern finds them (tests/test_abi.py), which stops at the digit.  tests/test_if2_host.py checks these the same way.
@@ -139,6 +139,8 @@ def load():
         "epipf_walk_smooth": ([P, i32, i32, i32, P, i32, P, P, P], i32),
         "epipf_run_incidence": ([P, i32, P, i32, i32, P, P, P, P, P, i32, i32, P, P], i32),
         "epipf_walk_smooth_history": ([P, i32, i32, i32, i32, i32, P, P, P, f64, i32, i32, P, i32, P, P, P], i32),
+        "epipf_incidence_walk": ([P, i32, P, i32, P, i32, P, P, P, P, i32, i32, P, P], i32),
+        "epipf_incidence_smooth": ([P, i32, i32, P, i32, i32, P, P, P], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -96,6 +96,7 @@ class Engine:
         self.T = 0                                       # rows of the observations (set_observations)
         self._run_T = None                               # rows of the last run, as the context holds them (last_T)
         self._last_n = None
+        self.run_serial = 0                              # filters run so far: each overwrites the resident history
 
     # ------------------------------------------------------------------ lifecycle
     def close(self):
@@ -136,8 +137,8 @@ class Engine:
     @property
     def run_T(self):
         """Rows of the last run's history: the observations' T after run / if2 / walk_filter, D + 2 after run_incidence
-        (before any run: T).  history(), path_sample(), smooth(), walk_history() and walk_smooth() are sized by it, as
-        the library writes them, whatever set_observations did since."""
+        and walk_incidence (before any run: T).  history(), path_sample(), smooth(), incidence_smooth(), walk_history()
+        and walk_smooth() are sized by it, as the library writes them, whatever set_observations did since."""
         return self.T if self._run_T is None else self._run_T
 
     # ------------------------------------------------------------------ the filter
@@ -168,6 +169,7 @@ class Engine:
                                             ptr(fidx), ptr(act), mode, ptr(ch), ptr(lz), ptr(st), ptr(tr)),
                   "epipf_run_sampled")
         self._last_n = n
+        self.run_serial += 1
         self._run_T = self.T
         self._last_status = st.copy()                    # Engine.smooth: rows of chains that did not run are NaN
         _PARTICLE_STEPS[0] += (n if act is None else int(np.count_nonzero(act))) * self.N * self.T
@@ -203,6 +205,7 @@ class Engine:
               "epipf_run_incidence")
         self._run_T = D + 2
         self._last_n = n
+        self.run_serial += 1
         self._last_status = st.copy()
         _PARTICLE_STEPS[0] += (n if act is None else int(np.count_nonzero(act))) * self.N * (D + 2)
         return lz, st
@@ -240,6 +243,7 @@ class Engine:
         check(getattr(self._L, entry)(self._h, S, M, ptr(swarm), d, ptr(hw), obs, ptr(probs), ptr(keys), ptr(f0),
                                       ptr(lz), ptr(mean), ptr(done), ptr(st)), entry)
         self._last_n = S
+        self.run_serial += 1
         self._run_T = self.T
         self._last_status = st.copy()
         _PARTICLE_STEPS[0] += int(np.minimum(done + 1, M).sum()) * self.N * self.T
@@ -416,10 +420,71 @@ class Engine:
         check(self._L.epipf_walk_filter(self._h, S, ptr(swarm), d, ptr(hw), obs, ptr(probs), ptr(keys), ptr(f), ptr(lz),
                                         ptr(st)), "epipf_walk_filter")
         self._last_n = S
+        self.run_serial += 1
         self._run_T = self.T
         self._last_status = st.copy()
         _PARTICLE_STEPS[0] += S * self.N * self.T
         return lz, st
+
+    def walk_incidence(self, swarm, half_widths, probs, keys, filter_index, counts, observations=False, cumulate=False):
+        """epipf_incidence_walk: the random-walk filter from the swarms [S, N, d] with chain s's half-widths
+        half_widths[s] ([S, d]), weighted by the reported transition counts `counts` [D, F] as run_incidence weighs
+        them.  Returns (log_zetas [S, D + 2], status [S]); run_T becomes D + 2, and history(), path_sample(), smooth(),
+        walk_history(), walk_smooth() and incidence_smooth() see the pass afterwards."""
+        swarm = np.ascontiguousarray(np.asarray(swarm, dtype=np.float64))
+        hw = np.ascontiguousarray(np.asarray(half_widths, dtype=np.float64))
+        if swarm.ndim != 3 or swarm.shape[1] != self.N:
+            raise ValueError(f"swarm must be [chains, {self.N}, d]")
+        S, _, d = swarm.shape
+        if hw.shape != (S, d):
+            raise ValueError(f"half_widths must be [{S}, {d}]")
+        counts = np.ascontiguousarray(np.asarray(counts, dtype=np.float64))
+        F = 2 if self.model == _lib.SIR else 3
+        if counts.ndim != 2 or counts.shape[1] != F:
+            raise ValueError(f"counts must be [D, {F}] for this model")
+        D = counts.shape[0]
+        probs = np.ascontiguousarray(np.broadcast_to(np.asarray(probs, dtype=np.float64), (S,)))
+        keys = np.ascontiguousarray(np.broadcast_to(np.asarray(keys, dtype=np.uint64), (S,)))
+        f = np.ascontiguousarray((np.broadcast_to(np.asarray(filter_index, dtype=np.uint64), (S,))
+                                  & np.uint64(0xFFFFFFFF)).astype(np.uint32))
+        lz = np.empty((S, D + 2), dtype=np.float64)
+        st = np.empty(S, dtype=np.int32)
+        obs = _lib.OBS_NORMAL if observations else _lib.OBS_BINOMIAL
+        check(self._L.epipf_incidence_walk(self._h, S, ptr(swarm), d, ptr(hw), obs, ptr(probs), ptr(keys), ptr(f),
+                                           ptr(counts), D, 1 if cumulate else 0, ptr(lz), ptr(st)), "epipf_incidence_walk")
+        self._last_n = S
+        self.run_serial += 1
+        self._run_T = D + 2
+        self._last_status = st.copy()
+        _PARTICLE_STEPS[0] += S * self.N * (D + 2)
+        return lz, st
+
+    def incidence_smooth(self, n_chains=None, quantiles=(0.05, 0.5, 0.95), bins=None, lag=None):
+        """epipf_incidence_smooth: the smoothed true flows per day of the last run_incidence or walk_incidence, reduced
+        on the device under the genealogy's multiplicities.  Returns Smoothed with a leading chain axis: mean
+        [n, D + 2, F], quantiles [n, Q, D + 2, F] or None, lineages [n, D + 2], sums [n, D + 2, F], zetas None; row 0 is
+        all zeros (no flow leads into the initial draw).  Rows of chains whose status was not OK are NaN in mean and 0
+        elsewhere.  bins defaults to the population total + 1 (no flow exceeds it).  lag=None is the full smoother."""
+        from . import smoothing
+        _, _, q = smoothing.check_options("genealogy", "smoothing", quantiles)
+        lag = smoothing.check_lag(lag, "smoothing")
+        n = int(n_chains) if n_chains is not None else self._last_n or 1
+        if bins is None:
+            if self._pop is None:
+                raise ValueError("bins=None needs set_population")
+            bins = int(sum(self._pop[0])) + 1
+        F = 2 if self.model == _lib.SIR else 3
+        nq = 0 if q is None else q.size
+        rows = max(n, 1)
+        sums = np.zeros((rows, self.run_T, F), dtype=np.int64)
+        lineages = np.zeros((rows, self.run_T), dtype=np.int32)
+        quant = np.zeros((rows, nq, self.run_T, F), dtype=np.int32) if nq else None
+        check(self._L.epipf_incidence_smooth(self._h, n, -1 if lag is None else min(lag, 2**31 - 1), ptr(q), nq,
+                                             int(bins) if nq else 0, ptr(sums), ptr(quant), ptr(lineages)),
+              "epipf_incidence_smooth")
+        mean = sums / float(self.N)
+        mean[self._last_status[:n] != _lib.STATUS_OK] = np.nan
+        return smoothing.Smoothed(mean, None if quant is None else quant.astype(np.int64), lineages, sums, None)
 
     def walk_history(self, n_chains=None):
         """theta [n, T, N, d] of the last walk_filter (epipf_walk_history)."""

@@ -93,20 +93,55 @@ def _check_probs(p, observations):
     return p
 
 
+def true_flows(mid, hidden, ancestry):
+    """flow [..., T, N, F] int64 of histories hidden [..., T, N, C], ancestry [..., T, N]: the flows above between each
+    particle's parent hidden[p-1][ancestry[p][i]] and its own state hidden[p][i]; row 0 is zeros.  What
+    Engine.incidence_smooth reduces, restated on the host."""
+    hid, anc = np.asarray(hidden, dtype=np.int64), np.asarray(ancestry, dtype=np.int64)
+    new = hid[..., 1:, :, :]
+    par = np.take_along_axis(hid[..., :-1, :, :], anc[..., 1:, :, None], axis=-2)
+    if mid == _lib.SIR:
+        cols = [par[..., 0] - new[..., 0], new[..., 2] - par[..., 2]]
+    else:
+        cols = [par[..., 0] - new[..., 0], (new[..., 2] + new[..., 3]) - (par[..., 2] + par[..., 3]),
+                new[..., 3] - par[..., 3]]
+    out = np.zeros(hid.shape[:-1] + (len(cols),), dtype=np.int64)
+    out[..., 1:, :, :] = np.stack(cols, axis=-1)
+    return out
+
+
 class IncidenceResult:
     """loglik [S]: the log-likelihood of every report per chain (-inf where the chain is not OK); log_zetas [S, D + 2];
     status [S] (STATUS_*); best: the argmax of loglik over the chains whose status is OK, or None when there is none;
     states: the `Smoothed` compartments of the run over its D + 2 rows (Engine.smooth), or None without quantiles;
-    history(): (hidden [S, D + 2, N, C], ancestry [S, D + 2, N]) of the run, valid until its engine runs again."""
+    incidence: the `Smoothed` true flows per day under the same quantiles and lag (Engine.incidence_smooth: mean
+    [S, D + 2, F] and quantiles [S, Q, D + 2, F] in the model's flow columns, row 0 zeros), or None without quantiles or
+    with lineage="reference"; history(): (hidden [S, D + 2, N, C], ancestry [S, D + 2, N]) of the run.  `incidence` is
+    reduced from the engine's resident history when it is first read and kept from then on.  Engines are shared
+    (`epipf.get_engine`), so another filter may have run on this one since: the read is then refused with a
+    RuntimeError instead of handing out that filter's flows (read `incidence` before the next run to keep it).
+    history() reads the resident history too and is the run's own until its engine runs again."""
 
-    def __init__(self, log_zetas, status, states, eng):
+    def __init__(self, log_zetas, status, states, eng, flows_options=None):
         self.log_zetas, self.status, self.states, self._eng = log_zetas, status, states, eng
+        self._flows_options, self._incidence = flows_options, None
+        # the engine's count of runs at this one (Engine.run_serial): what a later read of `incidence` is held against
+        self._serial = getattr(eng, "run_serial", None)
         ok = status == _lib.STATUS_OK
         self.loglik = np.where(ok, log_zetas[:, -1], -np.inf)
         self.best = int(np.argmax(self.loglik)) if ok.any() else None
 
     def history(self):
         return self._eng.history(self.status.shape[0])
+
+    @property
+    def incidence(self):
+        if self._incidence is None and self._flows_options is not None:
+            if self._serial is None or self._eng.run_serial != self._serial:
+                raise RuntimeError("the engine has run another filter since this one: its history, which `incidence` is "
+                                   "reduced from, is no longer this result's (read `incidence` before the next run)")
+            self._incidence = self._eng.incidence_smooth(self.status.shape[0], **self._flows_options)
+        return self._incidence
 
 
 def incidence_filter(cases, type_model, thetas, flows=("infections",), observations=False, probs=.5, n_particles=1000,
@@ -115,7 +150,10 @@ def incidence_filter(cases, type_model, thetas, flows=("infections",), observati
     """Run one filter per row of `thetas` ([d] or [chains, d]) on the reports (the module's docstring).  `probs` is a
     scalar or one per chain.  key / keys / filter_index default to the module stream (`epipf.seed_stream`): chain s
     under chain_key(key, s), all at one filter index taken from the stream's counter.  With `quantiles` the run is
-    smoothed on the device under `lineage` and `lag` (`epipf.smoothing`).  Returns IncidenceResult."""
+    smoothed on the device under `lineage` and `lag` (`epipf.smoothing`), and so are the particles' true flows
+    (`IncidenceResult.incidence`).  The flows are defined by a particle's true parent, so they exist under the
+    genealogy's multiplicities only: lineage="reference" leaves `incidence` None.  `incidence` is reduced when first
+    read, and refused if the engine has run again by then.  Returns IncidenceResult."""
     mid = _model(type_model)
     d = DIMS[mid]
     th = np.asarray(thetas, dtype=np.float64)
@@ -148,10 +186,12 @@ def incidence_filter(cases, type_model, thetas, flows=("infections",), observati
     eng.set_population(npop, mus)
     lz, st = eng.run_incidence(np.ascontiguousarray(th), np.broadcast_to(pr, (S,)), keys, f, counts,
                                observations=observations, cumulate=cumulate)
-    states = None
+    states = flows_options = None
     if quantiles is not None:
         states = eng.smooth(S, quantiles=quantiles, lineage=lineage, kind="smoothing", lag=lag)
-    return IncidenceResult(lz, st, states, eng)
+        if lineage == "genealogy":
+            flows_options = dict(quantiles=quantiles, lag=lag)
+    return IncidenceResult(lz, st, states, eng, flows_options)
 
 
 def incidence_mcmc(cases, type_model, parameters, h, sigma=None, iters=1000, flows=("infections",), observations=False,

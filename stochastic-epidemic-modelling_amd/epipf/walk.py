@@ -124,11 +124,14 @@ class WalkResult:
     [S, T]; status [S] (STATUS_*); theta_mean [S, T, d] and theta_quantiles [S, Q, T, d] (None without quantiles): the
     smoothed parameters per day; rt_mean [S, T] and rt_quantiles [S, Q, T]: R_t; lineages [S, T]; states: the
     `Smoothed` compartments of the same run under the same lineage and lag (Engine.smooth); best: the argmax of loglik
-    over the chains whose status is OK, or None when there is none.  Rows of chains that are not OK are NaN."""
+    over the chains whose status is OK, or None when there is none.  Rows of chains that are not OK are NaN.
+    incidence: None after walk_filter; after `epipf.walk_incidence_filter` the `Smoothed` true flows per day under the
+    same lag (Engine.incidence_smooth), or None under lineage="reference"."""
 
-    def __init__(self, log_zetas, status, mean, quant, lineages, states):
+    def __init__(self, log_zetas, status, mean, quant, lineages, states, incidence=None):
         d = mean.shape[-1] - 1
         self.log_zetas, self.status, self.lineages, self.states = log_zetas, status, lineages, states
+        self.incidence = incidence
         ok = status == _lib.STATUS_OK
         self.loglik = np.where(ok, log_zetas[:, -1], -np.inf)
         self.theta_mean, self.rt_mean = mean[..., :d], mean[..., d]
