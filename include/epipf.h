@@ -82,6 +82,7 @@ extern "C" {
 /* observation models: pmcmc.py:178-181 (observations=False / True) */
 #define EPIPF_OBS_BINOMIAL 0
 #define EPIPF_OBS_NORMAL 1
+#define EPIPF_OBS_NEGBIN 2 /* the incidence filters alone, through their *_negbin entry points */
 
 /* resampling: multinomial is the reference's (pmcmc.py:188); systematic is opt-in and changes results */
 #define EPIPF_RESAMPLE_MULTINOMIAL 0
@@ -463,6 +464,35 @@ int epipf_incidence_walk(epipf_ctx* ctx, int n_chains, const double* swarm_in, i
  * EPIPF_STATUS_OK are epipf_smooth_lag's. */
 int epipf_incidence_smooth(epipf_ctx* ctx, int n_chains, int lag, const double* q, int n_q, int bins, int64_t* sums_out,
                            int32_t* quant_out, int32_t* lineages_out);
+
+/* Negative-binomial reporting for the incidence filters: overdispersed case counts.  A report y of a
+ * column whose accumulated flow is n (acc_p[j][k] above) weighs, with rho = probs[s] (a mean ratio: it may exceed 1) and
+ * kappa = dispersion[s],
+ *   m = rho n;   m > 0 false: (y == 0 ? 1 : 0), a point mass at 0;   else, with t = kappa + m,
+ *   exp((c + kappa (log kappa - log t)) + y (log m - log t)),   c = lgamma(y + kappa) - lgamma(kappa) - lgamma(y + 1)
+ * in this order in plain doubles, log glibc's, c formed on the host in binary128 and rounded once (epipf_negbin_coefficients):
+ * the negative-binomial pmf of mean m and variance m + m^2 / kappa.  Everything else -- rows, the product over the
+ * reported columns, cumulate, degeneracy, resampling, Philox domains, the SSA, and the context's state afterwards -- is
+ * epipf_run_incidence's and epipf_incidence_walk's, whose arguments these take without obs_model and with
+ * dispersion [n_chains]; their validation and error texts hold, with these differences: a report must be an integer;
+ * an active chain's probs must be finite and >= 0 (and, being handed to a log that is defined for normal doubles, 0 or
+ * in [2^-1022, 2^990]); its dispersion must lie in [2^-1022, 1e6] -- the factor's rounding error is about
+ * kappa (|log kappa| + |log t|) 2^-53, 3e-9 at 1e6, and the Poisson limit beyond is out of scope.  The constants live in
+ * two device buffers of doubles, [n_chains][D+2][F] and [n_chains][2], allocated on first use, regrown on demand and
+ * freed by epipf_destroy. */
+int epipf_run_incidence_negbin(epipf_ctx* ctx, int n_chains, const double* theta, int d, const double* probs,
+                               const double* dispersion, const uint64_t* keys, const uint32_t* filter_index,
+                               const int32_t* active, const double* counts, int D, int cumulate, double* log_zetas_out,
+                               int32_t* status_out);
+int epipf_incidence_walk_negbin(epipf_ctx* ctx, int n_chains, const double* swarm_in, int d, const double* half_widths,
+                                const double* probs, const double* dispersion, const uint64_t* keys,
+                                const uint32_t* filter_index, const double* counts, int D, int cumulate,
+                                double* log_zetas_out, int32_t* status_out);
+
+/* out[i] = c(y[i], dispersion) as above (exactly 0 at y = 0): the constants the two entry points hand to the device.
+ * Host only; no GPU involved.  EPIPF_EINVAL for a y that is negative, infinite, NaN or not an integer, and for a
+ * dispersion outside (0, 1e6]. */
+int epipf_negbin_coefficients(const double* y, int n, double dispersion, double* out);
 
 /* The device's restatement of glibc's log (the reference's math.log / numpy legacy exponential),
  * evaluated on the host CPU with the same code and table: out[i] = log(x[i]) bit for bit for normal x[i] > 0.

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdarg>
 #include <cstddef>
@@ -152,6 +153,12 @@ struct epipf_ctx {
     size_t inc_counts_n = 0;
     int32_t* inc_acc = nullptr;
     size_t inc_acc_bytes = 0, inc_acc_limit = 0;
+    // negative-binomial reporting: the per-chain constants nb_coeff [chains][D + 2][F] and nb_chain
+    // [chains][2] (kappa, log kappa), written by the host alone; allocated beside the counts buffer on first use and
+    // regrown when a call needs more
+    double* nb_coeff = nullptr;
+    double* nb_chain = nullptr;
+    size_t nb_coeff_n = 0, nb_chain_n = 0;
     // while the context's history is an incidence pass's (epipf_run_incidence, epipf_incidence_walk): what
     // epipf_incidence_smooth reduces
     bool inc_valid = false;
@@ -356,7 +363,8 @@ static void free_ctx(epipf_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void* dev[] = {c->hidden, c->ancestry, c->res, c->chosen, c->traj, c->wraw, c->wloc, c->bsum,
-                   c->Y, c->lf, c->cp, c->logtab, c->scratch, c->abc, c->walk_theta, c->inc_counts, c->inc_acc};
+                   c->Y, c->lf, c->cp, c->logtab, c->scratch, c->abc, c->walk_theta, c->inc_counts, c->inc_acc,
+                   c->nb_coeff, c->nb_chain};
     for (void* p : dev)
         if (p) (void)hipFree(p);
     void* host[] = {c->h_cp, c->h_res, c->h_traj};
@@ -1648,8 +1656,9 @@ static int incidence_rows(const double* counts, int D, int F, int obs_model, std
         if (std::isnan(y)) continue;                                     // not reported
         if (std::isinf(y) || y < 0.0)
             return fail(EPIPF_EINVAL, "counts[%zu][%zu]=%g: a report must be finite and >= 0 (NaN: not reported)", i / F, i % F, y);
-        if (obs_model == EPIPF_OBS_BINOMIAL && y != std::floor(y))
-            return fail(EPIPF_EINVAL, "counts[%zu][%zu]=%g: the binomial model needs integer reports", i / F, i % F, y);
+        if (obs_model != EPIPF_OBS_NORMAL && y != std::floor(y))
+            return fail(EPIPF_EINVAL, "counts[%zu][%zu]=%g: the %s model needs integer reports", i / F, i % F, y,
+                        obs_model == EPIPF_OBS_NEGBIN ? "negative-binomial" : "binomial");
         rows[(size_t)F + i] = y;
         rep[1 + i / F] |= (uint8_t)(1u << (i % F));
     }
@@ -1695,13 +1704,74 @@ static int ensure_incidence_acc(epipf_ctx* c, int S, int F, int N) {
     return 0;
 }
 
+// Negative-binomial reporting.  negbin_check: a chain's dispersion and probs.  The device's log is
+// defined for normal doubles, so besides the model's own domain (dispersion in (0, 1e6], probs finite and >= 0) a
+// subnormal dispersion, a subnormal probs and a probs beyond 2^990 (whose mean probs x flow could overflow) are refused.
+// negbin_constants: the host's share of the factor, c(y, kappa) per (chain, row, column) and (kappa, log kappa) per
+// chain (negbin_coefficients, logfact.cpp), copied to the device buffers the kNegBin kernels read.
+constexpr double kNegBinMaxDispersion = 1e6;
+static int negbin_check(int ch, double kappa, double pr) {
+    if (!(kappa > 0.0 && kappa < INFINITY))
+        return fail(EPIPF_EINVAL, "dispersion[%d]=%g: the dispersion must be finite and > 0", ch, kappa);
+    if (kappa > kNegBinMaxDispersion)
+        return fail(EPIPF_EINVAL, "dispersion[%d]=%g: above 1e6 the factor's rounding error grows with the dispersion; the Poisson limit beyond it is out of scope", ch, kappa);
+    if (kappa < DBL_MIN) return fail(EPIPF_EINVAL, "dispersion[%d]=%g: a subnormal dispersion is out of scope", ch, kappa);
+    if (!(pr >= 0.0 && pr < INFINITY))
+        return fail(EPIPF_EINVAL, "probs[%d]=%g: the reporting ratio must be finite and >= 0", ch, pr);
+    if ((pr > 0.0 && pr < DBL_MIN) || pr > 0x1.0p990)
+        return fail(EPIPF_EINVAL, "probs[%d]=%g: a reporting ratio that is subnormal or above 2^990 is out of scope", ch, pr);
+    return 0;
+}
+
+static int ensure_doubles(epipf_ctx* c, double*& buf, size_t& have, size_t n) {
+    if (n > have) {
+        if (buf) { (void)hipStreamSynchronize(c->stream); (void)hipFree(buf); }
+        buf = nullptr;
+        have = 0;
+        if (dalloc(&buf, n)) return EPIPF_ENOMEM;
+        have = n;
+    }
+    return 0;
+}
+
+// rows [T][F] (NaN: not reported), dispersion [S] (checked).  coeff and chain stay alive until the stream is synchronised.
+static int negbin_constants(epipf_ctx* c, const std::vector<double>& rows, int S, int T, int F, const double* dispersion,
+                            std::vector<double>& coeff, std::vector<double>& chain, NegBinArgs& nb) {
+    coeff.resize((size_t)S * T * F);
+    chain.resize((size_t)S * 2);
+    for (int s = 0; s < S; ++s) {
+        chain[2 * (size_t)s] = dispersion[s];
+        chain[2 * (size_t)s + 1] = std::log(dispersion[s]);
+    }
+    negbin_coefficients(rows.data(), (size_t)T * F, dispersion, S, coeff.data());
+    if (const int e = ensure_doubles(c, c->nb_coeff, c->nb_coeff_n, coeff.size())) return e;
+    if (const int e = ensure_doubles(c, c->nb_chain, c->nb_chain_n, chain.size())) return e;
+    HIP_TRY(hipMemcpyAsync(c->nb_coeff, coeff.data(), sizeof(double) * coeff.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->nb_chain, chain.data(), sizeof(double) * chain.size(), hipMemcpyHostToDevice, c->stream));
+    nb.coeff = c->nb_coeff;
+    nb.chain = c->nb_chain;
+    return 0;
+}
+
+int epipf_negbin_coefficients(const double* y, int n, double dispersion, double* out) {
+    if (n < 0 || (n > 0 && (!y || !out))) return fail(EPIPF_EINVAL, "NULL argument");
+    if (!(dispersion > 0.0 && dispersion <= kNegBinMaxDispersion))
+        return fail(EPIPF_EINVAL, "dispersion=%g outside (0, 1e6]", dispersion);
+    for (int i = 0; i < n; ++i)
+        if (!(y[i] >= 0.0 && y[i] < INFINITY && y[i] == std::floor(y[i])))
+            return fail(EPIPF_EINVAL, "y[%d]=%g: a report must be an integer >= 0", i, y[i]);
+    negbin_coefficients(y, (size_t)n, &dispersion, 1, out);
+    return EPIPF_OK;
+}
+
 // The filter on reported transition counts: T = D + 2 rows (row 0 the initial draw, rows 1..D the days, row D + 1 one more
 // resampling on day D's weights), weights from the particles' flows (epipf_incidence.hpp).  hidden, ancestry, status and
 // log_zeta are the context's own and the run length becomes D + 2, so epipf_copy_history, epipf_path_sample, epipf_smooth
 // and epipf_smooth_lag see the pass afterwards.
-int epipf_run_incidence(epipf_ctx* c, int n_chains, const double* theta, int d, int obs_model, const double* probs,
-                        const uint64_t* keys, const uint32_t* filter_index, const int32_t* active, const double* counts,
-                        int D, int cumulate, double* log_zetas_out, int32_t* status_out) {
+// dispersion: null, or [n_chains] with obs_model = EPIPF_OBS_NEGBIN (epipf_run_incidence_negbin).
+static int run_incidence(epipf_ctx* c, int n_chains, const double* theta, int d, int obs_model, const double* probs,
+                         const uint64_t* keys, const uint32_t* filter_index, const int32_t* active, const double* counts,
+                         int D, int cumulate, double* log_zetas_out, int32_t* status_out, const double* dispersion) {
     if (!c || !theta || !probs || !keys || !filter_index || !counts || !log_zetas_out || !status_out)
         return fail(EPIPF_EINVAL, "NULL argument");
     if (c->model != EPIPF_SIR && c->model != EPIPF_SEIR)
@@ -1710,10 +1780,10 @@ int epipf_run_incidence(epipf_ctx* c, int n_chains, const double* theta, int d, 
     const int S = n_chains, N = c->N, F = incidence_flows(c->model);
     if (S < 1 || S > c->max_chains) return fail(EPIPF_EINVAL, "n_chains=%d outside [1, max_chains=%d]", S, c->max_chains);
     if (d != theta_dim(c->model, c->G)) return fail(EPIPF_EINVAL, "theta has %d entries per chain, model needs %d", d, theta_dim(c->model, c->G));
-    if (obs_model != EPIPF_OBS_BINOMIAL && obs_model != EPIPF_OBS_NORMAL) return fail(EPIPF_EINVAL, "bad obs_model %d", obs_model);
+    if (obs_model != EPIPF_OBS_BINOMIAL && obs_model != EPIPF_OBS_NORMAL && !dispersion) return fail(EPIPF_EINVAL, "bad obs_model %d", obs_model);
     if (D < 1 || (long long)D + 2 > c->Tmax) return fail(EPIPF_EINVAL, "D=%d: D + 2 rows outside [3, t_max=%d]", D, c->Tmax);
     const int T = D + 2;
-    std::vector<double> rows;
+    std::vector<double> rows, nb_coeff, nb_chain;
     std::vector<uint8_t> rep;
     if (const int e = incidence_rows(counts, D, F, obs_model, rows, rep)) return e;
     for (int ch = 0; ch < S; ++ch) {
@@ -1728,7 +1798,7 @@ int epipf_run_incidence(epipf_ctx* c, int n_chains, const double* theta, int d, 
         }
         const double pr = probs[ch];
         if (on)
-            if (const int e = incidence_probs(ch, pr, obs_model)) return e;
+            if (const int e = dispersion ? negbin_check(ch, dispersion[ch], pr) : incidence_probs(ch, pr, obs_model)) return e;
         set_chain_stream(c, q, pr, keys[ch], filter_index[ch]);
         q.skip = on ? 0 : 1;
         q.chosen = -1;
@@ -1753,9 +1823,17 @@ int epipf_run_incidence(epipf_ctx* c, int n_chains, const double* theta, int d, 
     s.Y = nullptr;                                       // the reports are a.counts
     a.counts = c->inc_counts; a.acc = cumulate ? c->inc_acc : nullptr; a.acc_half = acc_half;
 
+    NegBinArgs nb{};
+    if (dispersion) {
+        // a skipped chain's dispersion is not checked and not used: its constants are a valid chain's
+        std::vector<double> kap(dispersion, dispersion + S);
+        for (int ch = 0; ch < S; ++ch)
+            if (active && !active[ch]) kap[ch] = 1.0;
+        if (const int e = negbin_constants(c, rows, S, T, F, kap.data(), nb_coeff, nb_chain, nb)) return e;
+    }
     FilterStreams fs{};
     if (const int e = fork_streams(c, std::min(c->n_streams, S), fs)) return e;
-    const hipError_t le = launch_incidence(a, c->model, obs_model, cumulate != 0, rep.data(), S, fs);
+    const hipError_t le = launch_incidence(a, c->model, obs_model, cumulate != 0, rep.data(), S, fs, dispersion ? &nb : nullptr);
     if (le != hipSuccess) return fail(EPIPF_EHIP, "kernel launch failed: %s", hipGetErrorString(le));
     HIP_TRY(hipMemcpyAsync(log_zetas_out, c->log_zeta, sizeof(double) * (size_t)S * T, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(status_out, c->status, sizeof(int32_t) * S, hipMemcpyDeviceToHost, c->stream));
@@ -1786,13 +1864,30 @@ int epipf_run_incidence(epipf_ctx* c, int n_chains, const double* theta, int d, 
     return EPIPF_OK;
 }
 
+int epipf_run_incidence(epipf_ctx* c, int n_chains, const double* theta, int d, int obs_model, const double* probs,
+                        const uint64_t* keys, const uint32_t* filter_index, const int32_t* active, const double* counts,
+                        int D, int cumulate, double* log_zetas_out, int32_t* status_out) {
+    return run_incidence(c, n_chains, theta, d, obs_model, probs, keys, filter_index, active, counts, D, cumulate,
+                         log_zetas_out, status_out, nullptr);
+}
+
+int epipf_run_incidence_negbin(epipf_ctx* c, int n_chains, const double* theta, int d, const double* probs,
+                               const double* dispersion, const uint64_t* keys, const uint32_t* filter_index,
+                               const int32_t* active, const double* counts, int D, int cumulate, double* log_zetas_out,
+                               int32_t* status_out) {
+    if (!dispersion) return fail(EPIPF_EINVAL, "NULL argument");
+    return run_incidence(c, n_chains, theta, d, EPIPF_OBS_NEGBIN, probs, keys, filter_index, active, counts, D, cumulate,
+                         log_zetas_out, status_out, dispersion);
+}
+
 // ------------------------------------------------------------------------ R_t from case counts
 // The random-walk filter on reported transition counts: epipf_walk_filter's swarm, half-widths and theta_hist under
 // epipf_run_incidence's rows, reports and accumulator (epipf_walk_incidence.hpp).  The run length becomes D + 2 and the
 // parameter history is the context's, so the history calls of both parents see the pass afterwards.
-int epipf_incidence_walk(epipf_ctx* c, int n_chains, const double* swarm_in, int d, const double* half_widths, int obs_model,
-                         const double* probs, const uint64_t* keys, const uint32_t* filter_index, const double* counts,
-                         int D, int cumulate, double* log_zetas_out, int32_t* status_out) {
+// dispersion: null, or [n_chains] with obs_model = EPIPF_OBS_NEGBIN (epipf_incidence_walk_negbin).
+static int incidence_walk(epipf_ctx* c, int n_chains, const double* swarm_in, int d, const double* half_widths, int obs_model,
+                          const double* probs, const uint64_t* keys, const uint32_t* filter_index, const double* counts,
+                          int D, int cumulate, double* log_zetas_out, int32_t* status_out, const double* dispersion) {
     if (!c || !swarm_in || !half_widths || !probs || !keys || !filter_index || !counts || !log_zetas_out || !status_out)
         return fail(EPIPF_EINVAL, "NULL argument");
     if (c->model != EPIPF_SIR && c->model != EPIPF_SEIR)
@@ -1801,15 +1896,15 @@ int epipf_incidence_walk(epipf_ctx* c, int n_chains, const double* swarm_in, int
     const int S = n_chains, N = c->N, F = incidence_flows(c->model);
     if (d != theta_dim(c->model, c->G)) return fail(EPIPF_EINVAL, "theta has %d entries per particle, model needs %d", d, theta_dim(c->model, c->G));
     if (S < 1 || S > c->max_chains) return fail(EPIPF_EINVAL, "n_chains=%d outside [1, max_chains=%d]", S, c->max_chains);
-    if (obs_model != EPIPF_OBS_BINOMIAL && obs_model != EPIPF_OBS_NORMAL) return fail(EPIPF_EINVAL, "bad obs_model %d", obs_model);
+    if (obs_model != EPIPF_OBS_BINOMIAL && obs_model != EPIPF_OBS_NORMAL && !dispersion) return fail(EPIPF_EINVAL, "bad obs_model %d", obs_model);
     if (D < 1 || (long long)D + 2 > c->Tmax) return fail(EPIPF_EINVAL, "D=%d: D + 2 rows outside [3, t_max=%d]", D, c->Tmax);
     const int T = D + 2;
     if (const int e = check_swarm(half_widths, (size_t)S, swarm_in, (size_t)S, N, d)) return e;
-    std::vector<double> rows;
+    std::vector<double> rows, nb_coeff, nb_chain;
     std::vector<uint8_t> rep;
     if (const int e = incidence_rows(counts, D, F, obs_model, rows, rep)) return e;
     for (int s = 0; s < S; ++s) {
-        if (const int e = incidence_probs(s, probs[s], obs_model)) return e;
+        if (const int e = dispersion ? negbin_check(s, dispersion[s], probs[s]) : incidence_probs(s, probs[s], obs_model)) return e;
         ChainParam& q = c->h_cp[s];
         memset(&q, 0, sizeof q);                         // theta is the particles' own
         set_chain_stream(c, q, probs[s], keys[s], filter_index[s]);
@@ -1849,9 +1944,12 @@ int epipf_incidence_walk(epipf_ctx* c, int n_chains, const double* swarm_in, int
     a.d = d; a.hw = d_hw; a.start = d_start; a.hist = c->walk_theta; a.chain_stride = stride;
     a.counts = c->inc_counts; a.acc = cumulate ? c->inc_acc : nullptr; a.acc_half = acc_half;
 
+    NegBinArgs nb{};
+    if (dispersion)
+        if (const int e = negbin_constants(c, rows, S, T, F, dispersion, nb_coeff, nb_chain, nb)) return e;
     FilterStreams fs{};
     if (const int e = fork_streams(c, std::min(c->n_streams, S), fs)) return e;
-    const hipError_t le = launch_walk_incidence(a, c->model, obs_model, cumulate != 0, rep.data(), S, fs);
+    const hipError_t le = launch_walk_incidence(a, c->model, obs_model, cumulate != 0, rep.data(), S, fs, dispersion ? &nb : nullptr);
     if (le != hipSuccess) return fail(EPIPF_EHIP, "kernel launch failed: %s", hipGetErrorString(le));
     HIP_TRY(hipMemcpyAsync(log_zetas_out, c->log_zeta, sizeof(double) * (size_t)S * T, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(status_out, c->status, sizeof(int32_t) * S, hipMemcpyDeviceToHost, c->stream));
@@ -1876,6 +1974,22 @@ int epipf_incidence_walk(epipf_ctx* c, int n_chains, const double* swarm_in, int
     c->inc_valid = true;
     trim_scratch(c);
     return EPIPF_OK;
+}
+
+int epipf_incidence_walk(epipf_ctx* c, int n_chains, const double* swarm_in, int d, const double* half_widths, int obs_model,
+                         const double* probs, const uint64_t* keys, const uint32_t* filter_index, const double* counts,
+                         int D, int cumulate, double* log_zetas_out, int32_t* status_out) {
+    return incidence_walk(c, n_chains, swarm_in, d, half_widths, obs_model, probs, keys, filter_index, counts, D, cumulate,
+                          log_zetas_out, status_out, nullptr);
+}
+
+int epipf_incidence_walk_negbin(epipf_ctx* c, int n_chains, const double* swarm_in, int d, const double* half_widths,
+                                const double* probs, const double* dispersion, const uint64_t* keys,
+                                const uint32_t* filter_index, const double* counts, int D, int cumulate,
+                                double* log_zetas_out, int32_t* status_out) {
+    if (!dispersion) return fail(EPIPF_EINVAL, "NULL argument");
+    return incidence_walk(c, n_chains, swarm_in, d, half_widths, EPIPF_OBS_NEGBIN, probs, keys, filter_index, counts, D,
+                          cumulate, log_zetas_out, status_out, dispersion);
 }
 
 // The smoothed true flows of the last incidence pass: the flows of every particle formed on the device from the

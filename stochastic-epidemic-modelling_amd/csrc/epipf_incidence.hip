@@ -45,8 +45,11 @@ __global__ __launch_bounds__(64) void incidence_init_kernel(IncidenceArgs a) {
 }
 
 // rep_prev / rep_cur: bit k set where column k of day p - 1 / day p is reported
-template <int MODEL, int OBS, bool CUM>
-__global__ __launch_bounds__(64) void incidence_step_kernel(IncidenceArgs a, int p, int rep_prev, int rep_cur) {
+// NB: empty for the binomial and normal instances, whose signature and code are what they were; the kNegBin instances
+// take one NegBinArgs
+template <int MODEL, int OBS, bool CUM, class... NB>
+__global__ __launch_bounds__(64) void incidence_step_kernel(IncidenceArgs a, int p, int rep_prev, int rep_cur, NB... nb) {
+    static_assert(sizeof...(NB) == (OBS == kNegBin ? 1 : 0), "NegBinArgs goes with kNegBin alone");
     constexpr int C = Shape<MODEL, 1>::C;
     constexpr int F = incidence_flows(MODEL);
     constexpr int WG = 64;
@@ -90,7 +93,10 @@ __global__ __launch_bounds__(64) void incidence_step_kernel(IncidenceArgs a, int
     }
     // lanes the f32 loop could not run or could not certify: the exact loop from the untouched parent state, per lane
     // (one wave per block, so the test is block-uniform and the barrier legal)
-    if (__any(!fast_ok)) {
+    // (kNegBin: the weight's logs need the table as well, so a step with a reported column stages it whatever the lanes did)
+    bool stage = __any(!fast_ok);
+    if constexpr (OBS == kNegBin) stage = stage || (rep_cur != 0 && p + 1 < s.T);
+    if (stage) {
         for (int i = tid; i < kLogTabEntries; i += WG) tab[i] = s.logtab[i];
         __syncthreads();
         if (!fast_ok) nev = exact_propagate<MODEL, 1>(x, cp, (uint32_t)j, ptag, 1.0, tab, iters);
@@ -125,17 +131,29 @@ __global__ __launch_bounds__(64) void incidence_step_kernel(IncidenceArgs a, int
             }
             w = 1.0;
             const double* yrow = a.counts + (size_t)p * F;
+            if constexpr (OBS == kNegBin) {
+                const NegBinArgs& g = negbin_args(nb...);
+                const double EPIPF_CONSTANT* kc = (const double EPIPF_CONSTANT*)g.chain + (size_t)chain * 2;
+                const double EPIPF_CONSTANT* crow = (const double EPIPF_CONSTANT*)g.coeff + ((size_t)chain * s.T + p) * F;
+                const double kappa = kc[0], logk = kc[1];
 #pragma unroll
-            for (int k = 0; k < F; ++k)
-                if ((rep_cur >> k) & 1)                                                  // uniform branch
-                    w = w * incidence_factor<OBS>(yrow[k], (double)acc[k], cp, s.lf, s.lf_max);
+                for (int k = 0; k < F; ++k)
+                    if ((rep_cur >> k) & 1)                                              // uniform branch
+                        w = w * negbin_factor(yrow[k], (double)acc[k], cp.probs, crow[k], kappa, logk, tab);
+            } else {
+#pragma unroll
+                for (int k = 0; k < F; ++k)
+                    if ((rep_cur >> k) & 1)                                              // uniform branch
+                        w = w * incidence_factor<OBS>(yrow[k], (double)acc[k], cp, s.lf, s.lf_max);
+            }
         }
     }
     step_store_weights(s, smem, bp.b, j, p, w, wcur, bcur);
 }
 
-template <int MODEL, int OBS, bool CUM>
-static hipError_t launch_incidence_t(const IncidenceArgs& a, const uint8_t* rep, int n_chains, const FilterStreams& fs) {
+template <int MODEL, int OBS, bool CUM, class... NB>
+static hipError_t launch_incidence_t(const IncidenceArgs& a, const uint8_t* rep, int n_chains, const FilterStreams& fs,
+                                     NB... nb) {
     const StepArgs& s0 = a.s;
     const size_t lds = step_lds_bytes(s0.B, 64);
     launch_chain_groups(s0, n_chains, fs, 64, [&](int, const StepArgs& sg, int, dim3 grid, hipStream_t st) {
@@ -143,15 +161,18 @@ static hipError_t launch_incidence_t(const IncidenceArgs& a, const uint8_t* rep,
         ag.s = sg;
         hipLaunchKernelGGL((incidence_init_kernel<MODEL>), grid, dim3(64), lds, st, ag);
         for (int p = 1; p < s0.T; ++p)
-            hipLaunchKernelGGL((incidence_step_kernel<MODEL, OBS, CUM>), grid, dim3(64), lds, st, ag, p, (int)rep[p - 1],
-                               (int)rep[p]);
+            hipLaunchKernelGGL((incidence_step_kernel<MODEL, OBS, CUM, NB...>), grid, dim3(64), lds, st, ag, p,
+                               (int)rep[p - 1], (int)rep[p], nb...);
     });
     return hipGetLastError();
 }
 
 template <int MODEL>
 static hipError_t launch_incidence_m(const IncidenceArgs& a, int obs, bool cumulate, const uint8_t* rep, int n_chains,
-                                     const FilterStreams& fs) {
+                                     const FilterStreams& fs, const NegBinArgs* nb) {
+    if (obs == kNegBin)
+        return cumulate ? launch_incidence_t<MODEL, kNegBin, true>(a, rep, n_chains, fs, *nb)
+                        : launch_incidence_t<MODEL, kNegBin, false>(a, rep, n_chains, fs, *nb);
     if (obs == kBinomial)
         return cumulate ? launch_incidence_t<MODEL, kBinomial, true>(a, rep, n_chains, fs)
                         : launch_incidence_t<MODEL, kBinomial, false>(a, rep, n_chains, fs);
@@ -160,12 +181,13 @@ static hipError_t launch_incidence_m(const IncidenceArgs& a, int obs, bool cumul
 }
 
 hipError_t launch_incidence(const IncidenceArgs& a, int model, int obs, bool cumulate, const uint8_t* rep, int n_chains,
-                            const FilterStreams& fs) {
+                            const FilterStreams& fs, const NegBinArgs* nb) {
     if (a.s.wg != 64 || a.s.lanes != 1 || a.s.T < 3 || !a.counts || !rep || (cumulate && !a.acc))
         return hipErrorInvalidValue;
-    if (obs != kBinomial && obs != kNormal) return hipErrorInvalidValue;
-    if (model == kSIR) return launch_incidence_m<kSIR>(a, obs, cumulate, rep, n_chains, fs);
-    if (model == kSEIR) return launch_incidence_m<kSEIR>(a, obs, cumulate, rep, n_chains, fs);
+    if (obs != kBinomial && obs != kNormal && obs != kNegBin) return hipErrorInvalidValue;
+    if ((obs == kNegBin) != (nb != nullptr) || (nb && (!nb->coeff || !nb->chain))) return hipErrorInvalidValue;
+    if (model == kSIR) return launch_incidence_m<kSIR>(a, obs, cumulate, rep, n_chains, fs, nb);
+    if (model == kSEIR) return launch_incidence_m<kSEIR>(a, obs, cumulate, rep, n_chains, fs, nb);
     return hipErrorInvalidValue;
 }
 

@@ -264,6 +264,9 @@ static void launch_chain_groups(const StepArgs& a, int n, const FilterStreams& f
 // logfact.cpp (host, binary128): log n! and log p / log1p(-p) split into hi + lo doubles
 void logfact_table(int n_max, double* out);
 void log_p_split(double p, double* logp_hi, double* logp_lo, double* log1mp_hi, double* log1mp_lo);
+// out[s][i] = lgamma(y[i] + k[s]) - lgamma(k[s]) - lgamma(y[i] + 1) rounded once from binary128 (0 at y = 0 and at NaN):
+// the negative-binomial constants of n reports under each of S dispersions
+void negbin_coefficients(const double* y, size_t n, const double* k, int S, double* out);
 
 size_t step_lds_bytes(int B, int wg);
 size_t step_lds_bytes_seg(int B, int S, int wg);   // with S blocks per prefix segment (1: block sums in LDS)

@@ -25,8 +25,9 @@ struct WalkIncidenceArgs {
 
 // The T launches of a call (init and T - 1 = D + 1 steps), the chains split over the streams as launch_walk and
 // launch_incidence split them; no host synchronisation.  rep [T] as launch_incidence's.
+// nb: the kNegBin model's constants (obs == kNegBin), else null.
 hipError_t launch_walk_incidence(const WalkIncidenceArgs& a, int model, int obs, bool cumulate, const uint8_t* rep,
-                                 int n_chains, const FilterStreams& fs);
+                                 int n_chains, const FilterStreams& fs, const NegBinArgs* nb = nullptr);
 
 // The true flows of a resident history, for the smoother to reduce as a history of F compartments:
 //   flow [n][T][N][F] int32: row 0 zeros; row p >= 1, particle i: the §19 differences of hidden[p-1][ancestry[p][i]] and

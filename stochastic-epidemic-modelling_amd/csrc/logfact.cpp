@@ -12,6 +12,7 @@
 #include <cmath>
 #include <mutex>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 namespace {
@@ -89,6 +90,50 @@ void logfact_table(int n_max, double* out) {
 void log_p_split(double p, double* logp_hi, double* logp_lo, double* log1mp_hi, double* log1mp_lo) {
     split(logq((__float128)p), logp_hi, logp_lo);
     split(log1pq(-(__float128)p), log1mp_hi, log1mp_lo);
+}
+
+// The negative-binomial factor's constants: out[s][i] = lgamma(y[i] + k[s]) - lgamma(k[s]) -
+// lgamma(y[i] + 1) for integer reports y[i] >= 0 (NaN: not reported) and dispersions k[s] > 0, in binary128, rounded
+// once to double; exactly 0 at y = 0 and at NaN.  The three terms cancel to within a factor ~1e7 of the result at worst
+// (k = 1e6, y = 1), which leaves 113 - 24 bits: far beyond a double's 53.  lgammaq costs ~2 us, so the work is kept to
+// what differs: lgamma(y + 1) once per distinct report (case counts repeat), lgamma(k) once per chain, a chain whose
+// dispersion equals its predecessor's copies that row, and what is left -- one lgamma(y + k) per distinct report and
+// chain -- is dealt over up to 16 threads when there are more than 4096 of them.
+void negbin_coefficients(const double* y, size_t n, const double* k, int S, double* out) {
+    std::vector<double> ys;                              // the distinct reported y > 0
+    std::vector<int> slot(n, -1);                        // y[i]'s index in ys
+    std::unordered_map<double, int> seen;
+    for (size_t i = 0; i < n; ++i) {
+        if (std::isnan(y[i]) || y[i] == 0.0) continue;
+        const auto it = seen.emplace(y[i], (int)ys.size());
+        if (it.second) ys.push_back(y[i]);
+        slot[i] = it.first->second;
+    }
+    const size_t m = ys.size();
+    std::vector<__float128> lgy(m);
+    for (size_t j = 0; j < m; ++j) lgy[j] = lgammaq((__float128)ys[j] + 1);
+    const auto chains = [&](int from, int to) {
+        std::vector<double> c(m);
+        for (int s = from; s < to; ++s) {
+            double* row = out + (size_t)s * n;
+            if (s > from && k[s] == k[s - 1]) {
+                std::copy(row - n, row, row);
+                continue;
+            }
+            const __float128 kq = (__float128)k[s];
+            const __float128 lgk = lgammaq(kq);
+            for (size_t j = 0; j < m; ++j) c[j] = (double)(lgammaq((__float128)ys[j] + kq) - lgk - lgy[j]);
+            for (size_t i = 0; i < n; ++i) row[i] = slot[i] < 0 ? 0.0 : c[slot[i]];
+        }
+    };
+    const int threads = (size_t)S * m > 4096 ? (int)std::max(1u, std::min({16u, std::thread::hardware_concurrency(), (unsigned)S})) : 1;
+    if (threads == 1) {
+        chains(0, S);
+        return;
+    }
+    std::vector<std::thread> pool;
+    for (int t = 0; t < threads; ++t) pool.emplace_back(chains, (int)((long)S * t / threads), (int)((long)S * (t + 1) / threads));
+    for (auto& th : pool) th.join();
 }
 
 }  // namespace epipf

@@ -14,6 +14,7 @@ OK, EINVAL, EHIP, ENOMEM, ESTATE = 0, -1, -2, -3, -4
 STATUS_OK, STATUS_DEGENERATE, STATUS_SKIPPED = 0, 1, 2
 SIR, SEIR, SIR_SUBGROUPS, SIR_SUBGROUPS2 = 0, 1, 2, 3
 OBS_BINOMIAL, OBS_NORMAL = 0, 1
+OBS_NEGBIN = 2   # the incidence filters alone (epipf_run_incidence_negbin, epipf_incidence_walk_negbin)
 RESAMPLE_MULTINOMIAL, RESAMPLE_SYSTEMATIC = 0, 1
 PROFILE_OFF, PROFILE_TIMING, PROFILE_COUNTERS = 0, 1, 2
 LINEAGE_REFERENCE, LINEAGE_GENEALOGY = 0, 1
@@ -31,6 +32,7 @@ EXPORTS = (
     "epipf_iterated_filtering_subgroups", "epipf_smooth_lag", "epipf_smooth_lag_history", "epipf_forecast_summary",
     "epipf_walk_filter", "epipf_walk_history", "epipf_walk_smooth", "epipf_walk_smooth_history",
     "epipf_run_incidence", "epipf_incidence_walk", "epipf_incidence_smooth",
+    "epipf_run_incidence_negbin", "epipf_incidence_walk_negbin", "epipf_negbin_coefficients",
 )
 # Entry points whose names carry a digit, listed apart: EXPORTS is compared with the header's names as a letters-only
 # pattern finds them (tests/test_abi.py), which stops at the digit.  tests/test_if2_host.py checks these the same way.
@@ -141,6 +143,9 @@ def load():
         "epipf_walk_smooth_history": ([P, i32, i32, i32, i32, i32, P, P, P, f64, i32, i32, P, i32, P, P, P], i32),
         "epipf_incidence_walk": ([P, i32, P, i32, P, i32, P, P, P, P, i32, i32, P, P], i32),
         "epipf_incidence_smooth": ([P, i32, i32, P, i32, i32, P, P, P], i32),
+        "epipf_run_incidence_negbin": ([P, i32, P, i32, P, P, P, P, P, P, i32, i32, P, P], i32),
+        "epipf_incidence_walk_negbin": ([P, i32, P, i32, P, P, P, P, P, P, i32, i32, P, P], i32),
+        "epipf_negbin_coefficients": ([P, i32, f64, P], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -73,6 +73,17 @@ def theta_vector(mid, theta):
     return th, 1
 
 
+def dispersion_vector(dispersion, n, observations=False):
+    """A negative-binomial dispersion (a scalar or [n]) as contiguous float64 [n]; not with observations=True.  The values
+    are the callers' to check (epipf.incidence states the model's domain, the library refuses the rest)."""
+    if observations:
+        raise ValueError("dispersion is the negative-binomial model's: it does not go with observations=True")
+    kap = np.asarray(dispersion, dtype=np.float64)
+    if kap.shape not in ((), (n,)):
+        raise ValueError(f"dispersion must be a scalar or [{n}], got {kap.shape}")
+    return np.ascontiguousarray(np.broadcast_to(kap, (n,)))
+
+
 class Engine:
     def __init__(self, type_model, groups=1, n_particles=1000, t_max=1, max_chains=1, device=0):
         L = _lib.load()
@@ -176,11 +187,12 @@ class Engine:
         return (lz, st) if chosen is None else (lz, st, tr)
 
     def run_incidence(self, thetas, probs, keys, filter_indices, counts, observations=False, cumulate=False,
-                      active=None):
+                      active=None, dispersion=None):
         """epipf_run_incidence: len(thetas) filters on the reported transition counts `counts` [D, F] (F = 2 for SIR:
         infections, removals; 3 for SEIR: exposures, onsets, removals; NaN = not reported), shared by the chains.
         Returns (log_zetas [n, D + 2], status [n]); run_T becomes D + 2 (T stays the observations'), and history(),
-        path_sample() and smooth() see the pass afterwards."""
+        path_sample() and smooth() see the pass afterwards.  dispersion (a scalar or [n]): the reports are negative
+        binomial with mean probs x flow and this dispersion (epipf_run_incidence_negbin) instead."""
         thetas = np.ascontiguousarray(np.asarray(thetas, dtype=np.float64))
         if thetas.ndim != 2:
             raise ValueError("thetas must be [chains, d]")
@@ -199,10 +211,18 @@ class Engine:
             raise ValueError(f"active must have {n} entries")
         lz = np.empty((n, D + 2), dtype=np.float64)
         st = np.empty(n, dtype=np.int32)
-        obs = _lib.OBS_NORMAL if observations else _lib.OBS_BINOMIAL
-        check(self._L.epipf_run_incidence(self._h, n, ptr(thetas), thetas.shape[1], obs, ptr(probs), ptr(keys),
-                                          ptr(fidx), ptr(act), ptr(counts), D, 1 if cumulate else 0, ptr(lz), ptr(st)),
-              "epipf_run_incidence")
+        if dispersion is not None:
+            kap = dispersion_vector(dispersion, n, observations)
+            check(self._L.epipf_run_incidence_negbin(self._h, n, ptr(thetas), thetas.shape[1], ptr(probs), ptr(kap),
+                                                     ptr(keys), ptr(fidx), ptr(act), ptr(counts), D,
+                                                     1 if cumulate else 0, ptr(lz), ptr(st)),
+                  "epipf_run_incidence_negbin")
+        else:
+            obs = _lib.OBS_NORMAL if observations else _lib.OBS_BINOMIAL
+            check(self._L.epipf_run_incidence(self._h, n, ptr(thetas), thetas.shape[1], obs, ptr(probs), ptr(keys),
+                                              ptr(fidx), ptr(act), ptr(counts), D, 1 if cumulate else 0, ptr(lz),
+                                              ptr(st)),
+                  "epipf_run_incidence")
         self._run_T = D + 2
         self._last_n = n
         self.run_serial += 1
@@ -426,11 +446,13 @@ class Engine:
         _PARTICLE_STEPS[0] += S * self.N * self.T
         return lz, st
 
-    def walk_incidence(self, swarm, half_widths, probs, keys, filter_index, counts, observations=False, cumulate=False):
+    def walk_incidence(self, swarm, half_widths, probs, keys, filter_index, counts, observations=False, cumulate=False,
+                       dispersion=None):
         """epipf_incidence_walk: the random-walk filter from the swarms [S, N, d] with chain s's half-widths
         half_widths[s] ([S, d]), weighted by the reported transition counts `counts` [D, F] as run_incidence weighs
         them.  Returns (log_zetas [S, D + 2], status [S]); run_T becomes D + 2, and history(), path_sample(), smooth(),
-        walk_history(), walk_smooth() and incidence_smooth() see the pass afterwards."""
+        walk_history(), walk_smooth() and incidence_smooth() see the pass afterwards.  dispersion (a scalar or [S]):
+        negative-binomial reports instead (epipf_incidence_walk_negbin)."""
         swarm = np.ascontiguousarray(np.asarray(swarm, dtype=np.float64))
         hw = np.ascontiguousarray(np.asarray(half_widths, dtype=np.float64))
         if swarm.ndim != 3 or swarm.shape[1] != self.N:
@@ -449,9 +471,16 @@ class Engine:
                                   & np.uint64(0xFFFFFFFF)).astype(np.uint32))
         lz = np.empty((S, D + 2), dtype=np.float64)
         st = np.empty(S, dtype=np.int32)
-        obs = _lib.OBS_NORMAL if observations else _lib.OBS_BINOMIAL
-        check(self._L.epipf_incidence_walk(self._h, S, ptr(swarm), d, ptr(hw), obs, ptr(probs), ptr(keys), ptr(f),
-                                           ptr(counts), D, 1 if cumulate else 0, ptr(lz), ptr(st)), "epipf_incidence_walk")
+        if dispersion is not None:
+            kap = dispersion_vector(dispersion, S, observations)
+            check(self._L.epipf_incidence_walk_negbin(self._h, S, ptr(swarm), d, ptr(hw), ptr(probs), ptr(kap), ptr(keys),
+                                                      ptr(f), ptr(counts), D, 1 if cumulate else 0, ptr(lz), ptr(st)),
+                  "epipf_incidence_walk_negbin")
+        else:
+            obs = _lib.OBS_NORMAL if observations else _lib.OBS_BINOMIAL
+            check(self._L.epipf_incidence_walk(self._h, S, ptr(swarm), d, ptr(hw), obs, ptr(probs), ptr(keys), ptr(f),
+                                               ptr(counts), D, 1 if cumulate else 0, ptr(lz), ptr(st)),
+                  "epipf_incidence_walk")
         self._last_n = S
         self.run_serial += 1
         self._run_T = D + 2

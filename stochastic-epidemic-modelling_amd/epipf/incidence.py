@@ -26,6 +26,10 @@ is reported":
                   observations=False: the binomial pmf of the report out of acc_p[j][k] at `probs`
                   observations=True:  the normal pdf of the report at mean acc_p[j][k], sd probs acc_p[j][k] + 1e-4
 
+                  dispersion=k:       the negative-binomial pmf of the report at mean probs acc_p[j][k] and variance
+                                      mean + mean^2 / k: overdispersed reports, and a report may
+                                      exceed the particle's flow; probs is then a mean ratio and may exceed 1
+
 cumulate=False: a report counts that day alone and unreported days are simply unobserved; cumulate=True: a report counts
 everything since that column's previous report (weekly totals).  The product is the likelihood of independent reports.
 Resampling, random numbers, the SSA and the degeneracy rule are the filter's.  Scope: SIR and SEIR.
@@ -93,6 +97,33 @@ def _check_probs(p, observations):
     return p
 
 
+MAX_DISPERSION = 1e6
+
+
+def _check_dispersion(dispersion, observations, n=None):
+    """The negative-binomial dispersion as a float64 array, each entry in (0, 1e6]; with n, a scalar or
+    [n] broadcast to [n]."""
+    if n is None:
+        if observations:
+            raise ValueError("dispersion is the negative-binomial model's: it does not go with observations=True")
+        k = np.asarray(dispersion, dtype=np.float64)
+    else:
+        k = _engine.dispersion_vector(dispersion, n, observations)
+    if not (np.all(np.isfinite(k)) and np.all(k > 0.0)):
+        raise ValueError("dispersion must be finite and > 0")
+    if np.any(k > MAX_DISPERSION):
+        raise ValueError("dispersion must be <= 1e6: the Poisson limit beyond it is out of scope")
+    return k
+
+
+def _check_ratio(p):
+    """probs under a dispersion: a mean ratio, finite and >= 0."""
+    p = np.asarray(p, dtype=np.float64)
+    if not (np.all(np.isfinite(p)) and np.all(p >= 0.0)):
+        raise ValueError("probs must be finite and >= 0")
+    return p
+
+
 def true_flows(mid, hidden, ancestry):
     """flow [..., T, N, F] int64 of histories hidden [..., T, N, C], ancestry [..., T, N]: the flows above between each
     particle's parent hidden[p-1][ancestry[p][i]] and its own state hidden[p][i]; row 0 is zeros.  What
@@ -146,9 +177,10 @@ class IncidenceResult:
 
 def incidence_filter(cases, type_model, thetas, flows=("infections",), observations=False, probs=.5, n_particles=1000,
                      n_population=4820, mu=20, *, cumulate=False, key=None, keys=None, filter_index=None, device=0,
-                     quantiles=None, lineage="genealogy", lag=None):
+                     quantiles=None, lineage="genealogy", lag=None, dispersion=None):
     """Run one filter per row of `thetas` ([d] or [chains, d]) on the reports (the module's docstring).  `probs` is a
-    scalar or one per chain.  key / keys / filter_index default to the module stream (`epipf.seed_stream`): chain s
+    scalar or one per chain, and so is `dispersion` (None: the binomial or normal model; else negative-binomial
+    reports, not with observations=True).  key / keys / filter_index default to the module stream (`epipf.seed_stream`): chain s
     under chain_key(key, s), all at one filter index taken from the stream's counter.  With `quantiles` the run is
     smoothed on the device under `lineage` and `lag` (`epipf.smoothing`), and so are the particles' true flows
     (`IncidenceResult.incidence`).  The flows are defined by a particle's true parent, so they exist under the
@@ -166,8 +198,11 @@ def incidence_filter(cases, type_model, thetas, flows=("infections",), observati
     S, N = th.shape[0], int(n_particles)
     if N < 1:
         raise ValueError("n_particles must be >= 1")
+    extra = {}
+    if dispersion is not None:
+        extra["dispersion"] = _check_dispersion(dispersion, observations, S)
     counts = counts_matrix(cases, mid, flows, observations)
-    pr = _check_probs(probs, observations)
+    pr = _check_probs(probs, observations) if dispersion is None else _check_ratio(probs)
     if pr.shape not in ((), (S,)):
         raise ValueError(f"probs must be a scalar or [{S}], got {pr.shape}")
     if quantiles is not None:
@@ -185,7 +220,7 @@ def incidence_filter(cases, type_model, thetas, flows=("infections",), observati
     eng = _engine.get_engine(mid, 1, N, counts.shape[0] + 2, S, device)
     eng.set_population(npop, mus)
     lz, st = eng.run_incidence(np.ascontiguousarray(th), np.broadcast_to(pr, (S,)), keys, f, counts,
-                               observations=observations, cumulate=cumulate)
+                               observations=observations, cumulate=cumulate, **extra)
     states = flows_options = None
     if quantiles is not None:
         states = eng.smooth(S, quantiles=quantiles, lineage=lineage, kind="smoothing", lag=lag)
@@ -196,7 +231,7 @@ def incidence_filter(cases, type_model, thetas, flows=("infections",), observati
 
 def incidence_mcmc(cases, type_model, parameters, h, sigma=None, iters=1000, flows=("infections",), observations=False,
                    probs=.5, n_particles=1000, n_population=4820, mu=20, *, cumulate=False, chains=1, seed=0, rngs=None,
-                   keys=None, device=0, filter_index_start=0):
+                   keys=None, device=0, filter_index_start=0, dispersion=None):
     """Random-walk Metropolis-Hastings on the incidence likelihood, `chains` chains in lockstep with one batched filter
     call per iteration.  parameters: the starting theta [d] or [chains, d] (with probs=None its last entry is the
     reporting probability, estimated with the rates); proposals are N(theta, h sigma) (sigma: identity, [d, d] or
@@ -210,6 +245,11 @@ def incidence_mcmc(cases, type_model, parameters, h, sigma=None, iters=1000, flo
     proposal is accepted iff it is valid, its filter is OK and log u < lz_new - lz_old, lz = log_zetas[:, D + 1]; one
     more legacy_randint(N) then picks the trajectory (D + 2 rows), otherwise the previous row is copied.
 
+    dispersion: a scalar fixes the negative-binomial dispersion; "estimate" appends it as the last
+    entry of `parameters` (after the reporting probability when probs=None) and a proposal whose dispersion is <= 0 or
+    > 1e6 is invalid in the same way.  With a dispersion the reporting probability is a mean ratio: any value >= 0 is
+    valid.  Not with observations=True.
+
     Returns a list of ChainResult (thetas [iters, d], likelihoods, log_likelihoods [iters], sampled_trajs
     [D + 2, iters, C], acceptances = accepted proposals, filters_run)."""
     mid = _model(type_model)
@@ -217,19 +257,32 @@ def incidence_mcmc(cases, type_model, parameters, h, sigma=None, iters=1000, flo
     if nc < 1 or N < 1 or iters < 1:
         raise ValueError("chains, n_particles and iters must be >= 1")
     dm = DIMS[mid]
-    d = dm + (1 if probs is None else 0)
+    est_k = isinstance(dispersion, str)
+    if est_k and dispersion != "estimate":
+        raise ValueError('dispersion must be None, a scalar or "estimate"')
+    if dispersion is not None and observations:
+        raise ValueError("dispersion is the negative-binomial model's: it does not go with observations=True")
+    d = dm + (1 if probs is None else 0) + (1 if est_k else 0)
+    ip = dm if probs is None else None                   # the reporting probability's column of `parameters`
     P = np.asarray(parameters, dtype=np.float64)
     if P.shape not in ((d,), (nc, d)):
         raise ValueError(f"parameters must be [{d}] or [{nc}, {d}], got {P.shape}")
     P = np.ascontiguousarray(np.broadcast_to(P, (nc, d)))
     if not (np.all(np.isfinite(P)) and np.all(P >= 0.0)):
         raise ValueError("parameters must be finite and >= 0")
+    check_p = _check_probs if dispersion is None else (lambda p, _obs: _check_ratio(p))
     if probs is None:
-        _check_probs(P[:, -1], observations)
+        check_p(P[:, ip], observations)
     else:
         if np.ndim(probs) != 0:
             raise ValueError("probs must be a scalar, or None to estimate it as the last parameter")
-        _check_probs(probs, observations)
+        check_p(probs, observations)
+    if est_k:
+        _check_dispersion(P[:, -1], observations)
+    elif dispersion is not None:
+        if np.ndim(dispersion) != 0:
+            raise ValueError('dispersion must be a scalar, or "estimate" to estimate it as the last parameter')
+        _check_dispersion(dispersion, observations)
     if not (np.isfinite(h) and h > 0):
         raise ValueError("h must be finite and > 0")
     Sg = np.eye(d) if sigma is None else np.asarray(sigma, dtype=np.float64)
@@ -254,9 +307,13 @@ def incidence_mcmc(cases, type_model, parameters, h, sigma=None, iters=1000, flo
 
     def split(theta):
         """(rates [nc, dm], probs [nc]) of full parameter rows"""
-        if probs is None:
-            return theta[:, :dm], theta[:, -1]
-        return theta, np.full(nc, float(probs))
+        return theta[:, :dm], (theta[:, ip] if probs is None else np.full(nc, float(probs)))
+
+    def extra(theta):
+        """the engine call's dispersion keyword: none without a dispersion"""
+        if dispersion is None:
+            return {}
+        return {"dispersion": np.ascontiguousarray(theta[:, -1]) if est_k else np.full(nc, float(dispersion))}
 
     thetas = np.zeros((nc, iters, d))
     loglik = np.zeros((nc, iters))
@@ -267,7 +324,7 @@ def incidence_mcmc(cases, type_model, parameters, h, sigma=None, iters=1000, flo
 
     th0, pr0 = split(P)
     lz, st = eng.run_incidence(np.ascontiguousarray(th0), pr0, keys, fnext.astype(np.uint64), counts,
-                               observations=observations, cumulate=cumulate)
+                               observations=observations, cumulate=cumulate, **extra(P))
     fnext += 1
     filters_run += 1
     for c in range(nc):
@@ -290,8 +347,10 @@ def incidence_mcmc(cases, type_model, parameters, h, sigma=None, iters=1000, flo
             u = rngs[c].random_sample()
             logu[c] = np.log(u) if u > 0.0 else -np.inf
             ok = not (props[c] < 0).any()
-            if ok and probs is None:
-                ok = 0.0 <= props[c, -1] <= 1.0
+            if ok and probs is None and dispersion is None:
+                ok = 0.0 <= props[c, ip] <= 1.0
+            if ok and est_k:
+                ok = 0.0 < props[c, -1] <= MAX_DISPERSION
             if ok:
                 act[c] = 1
                 fidx[c] = fnext[c]
@@ -299,9 +358,10 @@ def incidence_mcmc(cases, type_model, parameters, h, sigma=None, iters=1000, flo
                 filters_run[c] += 1
         take = np.zeros(nc, dtype=bool)
         if act.any():
-            th_all, pr_all = split(np.where(act[:, None] != 0, props, thetas[:, i - 1]))
+            full = np.where(act[:, None] != 0, props, thetas[:, i - 1])
+            th_all, pr_all = split(full)
             lz, st = eng.run_incidence(np.ascontiguousarray(th_all), pr_all, keys, fidx, counts,
-                                       observations=observations, cumulate=cumulate, active=act)
+                                       observations=observations, cumulate=cumulate, active=act, **extra(full))
             for c in range(nc):
                 take[c] = bool(act[c]) and st[c] == _lib.STATUS_OK and logu[c] < lz[c, -1] - loglik[c, i - 1]
         if take.any():

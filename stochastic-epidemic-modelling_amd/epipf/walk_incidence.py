@@ -23,17 +23,18 @@ import numpy as np
 
 from . import engine as _engine
 from . import smoothing
-from .incidence import _check_probs, _model, counts_matrix
+from .incidence import _check_dispersion, _check_probs, _check_ratio, _model, counts_matrix
 from .pmcmc import _STREAM, _population, _take_filter_index, chain_key
 from .walk import DIMS, WalkResult
 
 
 def walk_incidence_filter(cases, type_model, start, rw, flows=("infections",), *, observations=False, probs=.5,
                           cumulate=False, lag=10, quantiles=smoothing.DEFAULT_QUANTILES, lineage="genealogy",
-                          n_particles=1000, n_population=4820, mu=20, chains=1, key=None, device=0):
+                          n_particles=1000, n_population=4820, mu=20, chains=1, key=None, device=0, dispersion=None):
     """Run `chains` random-walk filters on the reports and smooth their parameter histories, states and true flows on
     the device (the module's docstring).  `start` is [d] (every particle starts there), [N, d] or [chains, N, d]; `rw`
-    is [d] or [chains, d] (>= 0); `probs` is a scalar or one per chain.  lag=None is the full smoother.  Returns
+    is [d] or [chains, d] (>= 0); `probs` is a scalar or one per chain, and so is `dispersion` (None: the binomial or
+    normal model; else negative-binomial reports, `epipf.incidence`; not with observations=True).  lag=None is the full smoother.  Returns
     WalkResult with `incidence`."""
     mid = _model(type_model)
     d = DIMS[mid]
@@ -52,8 +53,11 @@ def walk_incidence_filter(cases, type_model, start, rw, flows=("infections",), *
         raise ValueError("rw and start must be finite and >= 0")
     swarm = np.ascontiguousarray(np.broadcast_to(start, (S, N, d)))
     hw = np.ascontiguousarray(np.broadcast_to(rw, (S, d)))
+    extra = {}
+    if dispersion is not None:
+        extra["dispersion"] = _check_dispersion(dispersion, observations, S)
     counts = counts_matrix(cases, mid, flows, observations)
-    pr = _check_probs(probs, observations)
+    pr = _check_probs(probs, observations) if dispersion is None else _check_ratio(probs)
     if pr.shape not in ((), (S,)):
         raise ValueError(f"probs must be a scalar or [{S}], got {pr.shape}")
     npop, mus = _population(mid, 1, n_population, mu)
@@ -63,7 +67,7 @@ def walk_incidence_filter(cases, type_model, start, rw, flows=("infections",), *
     eng = _engine.get_engine(mid, 1, N, counts.shape[0] + 2, S, device)
     eng.set_population(npop, mus)
     lz, st = eng.walk_incidence(swarm, hw, np.broadcast_to(pr, (S,)), keys, f, counts, observations=observations,
-                                cumulate=cumulate)
+                                cumulate=cumulate, **extra)
     mean, quant, lineages = eng.walk_smooth(S, quantiles=quantiles, lineage=lineage, lag=lag)
     states = eng.smooth(S, quantiles=quantiles, lineage=lineage, kind="smoothing", lag=lag)
     true_flows = eng.incidence_smooth(S, quantiles=quantiles, lag=lag) if lineage == "genealogy" else None
